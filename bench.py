@@ -10,7 +10,15 @@ level while the LLM still decodes every step.  Multi-GPU: one p
 GPU, independent utterances per rank (batch-sharded streams, no data-path collective),
 max-over-ranks time, ``scaling: weak``.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline RTF,
+``ms_per_step``, first-audio latency).  ``--dump-outputs DIR`` also writes what the last timed
+step handed its caller as ``DIR/pcm.npy`` (float32, the PCM16 samples) and
+``DIR/token_ids.npy`` (float64); inputs are seeded, so two builds run with the same arguments
+can be compared output for output.  ``--full`` adds every other section to the same line: the
+HTTP-level runs, configs[2] / [3] / [4], the per-kernel and roofline figures and the CPU
+baseline.
 
 ``--gpus N`` without a launcher (no ``WORLD_SIZE`` in the environment) starts the N rank
 processes itself, one per GPU, before anything touches a GPU (``launch_ranks``); under
@@ -39,6 +47,13 @@ def parse():
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--max-tokens", type=int, default=MAX_TOKENS)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other section: HTTP level, "
+                        "configs[2] / [3] / [4], per-kernel and roofline figures, CPU baseline "
+                        "(the options below shape those sections)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step's caller received (PCM, token ids) "
+                        "as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--profile-steps", type=int, default=24)
     p.add_argument("--batch", type=int, default=32,
@@ -568,80 +583,11 @@ def run_fp8(args, cfg, local, snac, prompt, inject, rank, world, dist):
     return out
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch_ranks(args.gpus))
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} ranks")
-    if args.dry_run:
-        dry_run(args, rank, world)
-        return
-    import numpy as np
+def full_sections(args, cfg, llm, snac, syn, prompt, inject, rank, world, local, dist, audio):
+    """``--full``: everything the benchmark measures beside the headline figure, on the
+    engines the timed steps used; returns the result line's further keys (rank 0's hold the
+    figures)."""
     import torch
-    import torch.distributed as dist
-
-    if world > 1:
-        torch.cuda.set_device(local)
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    torch.cuda.set_device(local)
-
-    from project_morpheus_amd import config as C
-    from project_morpheus_amd import inference as I
-    from project_morpheus_amd.engine import (LlmEngine, SnacDecoder, Synthesizer,
-                                             UtteranceStats)
-    from project_morpheus_amd.tokenizer import Tokenizer
-    from project_morpheus_amd.weights import synthetic_llm_weights, synthetic_snac_weights
-
-    cfg = C.OrpheusConfig()
-    free0 = torch.cuda.mem_get_info(local)[0]
-    w = synthetic_llm_weights(cfg, seed=0, device=f"cuda:{local}")
-    B3 = args.batch
-    llm = LlmEngine(cfg, w, device=local, max_slots=max(1, B3), max_pos=2048,
-                    max_batch=max(1, B3), max_prefill=512)
-    del w
-    torch.cuda.empty_cache()
-    # device memory the engine holds (driver view): bf16 weights row-major for the one-row
-    # GEMVs + the fragment-major copies the multi-row GEMMs read, KV cache and workspaces
-    engine_hbm_gb = round((free0 - torch.cuda.mem_get_info(local)[0]) / 1e9, 2)
-    snac = SnacDecoder(synthetic_snac_weights(), device=local, max_frames=7,
-                       max_batch=max(1, B3))
-    syn = Synthesizer(llm, snac, depth=3, seed=rank)
-    tok = Tokenizer(None)
-    prompt = I.prompt_ids(tok.encode("tara: Hello world"))
-    inject = synthetic_audio_ids(args.max_tokens, seed=2 + rank)
-
-    def utterance():
-        st = UtteranceStats()
-        for _ in syn.run(prompt, args.max_tokens, 1.1, stop_ids=(), inject_ids=inject, stats=st):
-            pass
-        return st
-
-    for _ in range(args.warmup):
-        utterance()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    stats = [utterance() for _ in range(args.steps)]
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    audio = sum(s.audio_seconds for s in stats)
-    firsts = [s.first_audio_ms for s in stats]
-    if world > 1:
-        t = torch.tensor([elapsed], device="cuda")
-        a = torch.tensor([audio], device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dist.all_reduce(a, op=dist.ReduceOp.SUM)
-        elapsed, audio = float(t.item()), float(a.item())
-        fl = [None] * world
-        dist.all_gather_object(fl, firsts)
-        firsts = [x for r in fl for x in r]
 
     # ---- configs[1] at the HTTP level (rank 0 only: one request through the ASGI app) ----
     http_level = http_orch = http_service = ceiling = None
@@ -654,7 +600,7 @@ def main():
 
     # ---- configs[2]: B concurrent streams per GPU, continuous batching + batched SNAC ----
     batched = batched_nc = None
-    if B3 > 0:
+    if args.batch > 0:
         batched = run_batched(args, llm, snac, prompt, rank, world, dist)
         if args.compaction_ab:
             batched_nc = run_batched(args, llm, snac, prompt, rank, world, dist,
@@ -709,11 +655,144 @@ def main():
     llm.release_row(0, st)
     st.synchronize()
 
+    if rank != 0:
+        return {}
+    res = {
+        "http_level": http_level,
+        "http_level_orchestrator": http_orch,
+        "http_level_service": http_service,
+        "orchestrator_ceiling": ceiling,
+        "configs_2_batched": batched,
+        **({"configs_2_no_compaction": batched_nc} if batched_nc else {}),
+        "configs_3_long_read": long_read,
+        "configs_4_fp8": fp8,
+        "decode_step_ms": round(step_ms, 4),
+        "decode_tok_per_s": round(1e3 / step_ms, 1),
+        "step_roofline": {"bytes": step_bytes, "achieved_gbs": round(step_bytes / step_ms / 1e6, 1),
+                          "frac": round(step_bytes / step_ms / 1e6 / PEAK_HBM_GBS, 4)},
+        "roofline": {"kernel": ROOFLINE_KERNEL,
+                     "what": "one-row RMSNorm + gate/up [16384 x 3072] + SiLU*up (EPI_SILU, NORM)",
+                     "bound": "hbm", "achieved": round(gu_gbs, 1), "peak": PEAK_HBM_GBS,
+                     "unit": "GB/s", "frac": round(gu_gbs / PEAK_HBM_GBS, 4),
+                     "avg_launch_us": round(gu_us, 3), "bytes_per_launch": gu_bytes,
+                     "avg_launch_us_source": "HIP events around one hipGraph of 4 x 28 "
+                                             "back-to-back launches (launch gaps included)",
+                     **rocprof_fields(gu_bytes),
+                     "traffic": pmc_traffic("gate_up"),
+                     "traffic_source": f"profiles/{PMC_RECORD} (rocprofv3 --pmc "
+                                       "FETCH_SIZE / WRITE_SIZE, separate passes)"},
+        "eager_step_us_by_kernel": per_step_us,
+        "gemv_graph_us": {k: {"us": round(v[0], 2), "GB/s": round(v[1] / v[0] / 1e3, 1)}
+                          for k, v in gemv_us.items()},
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        res["cpu_baseline"] = cpu_baseline(cfg, prompt)
+    return res
+
+
+def dump_outputs(path, rank, pcm_chunks, token_ids):
+    """``--dump-outputs``: what the caller of the last timed utterance received, as float .npy
+    files (rank 0 under the plain names, rank r > 0 as ``<name>.rank<r>.npy``): ``pcm`` = the
+    PCM16 chunks ``Synthesizer.run`` yielded, joined in order; ``token_ids`` = the ids the LLM
+    decoded (``UtteranceStats.token_ids``).  Both are exact in the float types used."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = f".rank{rank}" if rank else ""
+    pcm = np.frombuffer(b"".join(pcm_chunks), dtype=np.int16).astype(np.float32)
+    np.save(os.path.join(path, f"pcm{sfx}.npy"), pcm)
+    np.save(os.path.join(path, f"token_ids{sfx}.npy"), np.asarray(token_ids, dtype=np.float64))
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(launch_ranks(args.gpus))
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} ranks")
+    if args.dry_run:
+        dry_run(args, rank, world)
+        return
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    if world > 1:
+        torch.cuda.set_device(local)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    torch.cuda.set_device(local)
+
+    from project_morpheus_amd import config as C
+    from project_morpheus_amd import inference as I
+    from project_morpheus_amd.engine import (LlmEngine, SnacDecoder, Synthesizer,
+                                             UtteranceStats)
+    from project_morpheus_amd.tokenizer import Tokenizer
+    from project_morpheus_amd.weights import synthetic_llm_weights, synthetic_snac_weights
+
+    cfg = C.OrpheusConfig()
+    free0 = torch.cuda.mem_get_info(local)[0]
+    w = synthetic_llm_weights(cfg, seed=0, device=f"cuda:{local}")
+    B3 = args.batch
+    llm = LlmEngine(cfg, w, device=local, max_slots=max(1, B3), max_pos=2048,
+                    max_batch=max(1, B3), max_prefill=512)
+    del w
+    torch.cuda.empty_cache()
+    # device memory the engine holds (driver view): bf16 weights row-major for the one-row
+    # GEMVs + the fragment-major copies the multi-row GEMMs read, KV cache and workspaces
+    engine_hbm_gb = round((free0 - torch.cuda.mem_get_info(local)[0]) / 1e9, 2)
+    snac = SnacDecoder(synthetic_snac_weights(), device=local, max_frames=7,
+                       max_batch=max(1, B3))
+    syn = Synthesizer(llm, snac, depth=3, seed=rank)
+    tok = Tokenizer(None)
+    prompt = I.prompt_ids(tok.encode("tara: Hello world"))
+    inject = synthetic_audio_ids(args.max_tokens, seed=2 + rank)
+
+    def utterance(keep=None):
+        st = UtteranceStats()
+        for pcm in syn.run(prompt, args.max_tokens, 1.1, stop_ids=(), inject_ids=inject,
+                           stats=st):
+            if keep is not None:
+                keep.append(pcm)
+        return st
+
+    for _ in range(args.warmup):
+        utterance()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    last_pcm = []   # --dump-outputs: the chunks the last timed utterance yields
+    t0 = time.perf_counter()
+    stats = [utterance(last_pcm if args.dump_outputs and i == args.steps - 1 else None)
+             for i in range(args.steps)]
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    elapsed = time.perf_counter() - t0
+    audio = sum(s.audio_seconds for s in stats)
+    firsts = [s.first_audio_ms for s in stats]
+    if world > 1:
+        t = torch.tensor([elapsed], device="cuda")
+        a = torch.tensor([audio], device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dist.all_reduce(a, op=dist.ReduceOp.SUM)
+        elapsed, audio = float(t.item()), float(a.item())
+        fl = [None] * world
+        dist.all_gather_object(fl, firsts)
+        firsts = [x for r in fl for x in r]
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last_pcm, stats[-1].token_ids)
+
+    more = {}
+    if args.full:
+        more = full_sections(args, cfg, llm, snac, syn, prompt, inject, rank, world, local,
+                             dist, audio)
+
     if rank == 0:
-        steps_audio = audio
-        value = steps_audio / elapsed
         res = {
-            "metric": METRIC, "value": round(value, 4), "unit": "audio-sec/wall-sec",
+            "metric": METRIC, "value": round(audio / elapsed, 4), "unit": "audio-sec/wall-sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -725,36 +804,9 @@ def main():
                        "max_tokens": args.max_tokens, "parallelism": f"streams{world}"},
             "p50_first_audio_ms": round(statistics.median(firsts), 2),
             "audio_seconds": round(audio, 3),
-            "http_level": http_level,
-            "http_level_orchestrator": http_orch,
-            "http_level_service": http_service,
-            "orchestrator_ceiling": ceiling,
-            "configs_2_batched": batched,
-            **({"configs_2_no_compaction": batched_nc} if batched_nc else {}),
-            "configs_3_long_read": long_read,
-            "configs_4_fp8": fp8,
             "engine_hbm_gb": engine_hbm_gb,
-            "decode_step_ms": round(step_ms, 4),
-            "decode_tok_per_s": round(1e3 / step_ms, 1),
-            "step_roofline": {"bytes": step_bytes, "achieved_gbs": round(step_bytes / step_ms / 1e6, 1),
-                              "frac": round(step_bytes / step_ms / 1e6 / PEAK_HBM_GBS, 4)},
-            "roofline": {"kernel": ROOFLINE_KERNEL,
-                         "what": "one-row RMSNorm + gate/up [16384 x 3072] + SiLU*up (EPI_SILU, NORM)",
-                         "bound": "hbm", "achieved": round(gu_gbs, 1), "peak": PEAK_HBM_GBS,
-                         "unit": "GB/s", "frac": round(gu_gbs / PEAK_HBM_GBS, 4),
-                         "avg_launch_us": round(gu_us, 3), "bytes_per_launch": gu_bytes,
-                         "avg_launch_us_source": "HIP events around one hipGraph of 4 x 28 "
-                                                 "back-to-back launches (launch gaps included)",
-                         **rocprof_fields(gu_bytes),
-                         "traffic": pmc_traffic("gate_up"),
-                         "traffic_source": f"profiles/{PMC_RECORD} (rocprofv3 --pmc "
-                                           "FETCH_SIZE / WRITE_SIZE, separate passes)"},
-            "eager_step_us_by_kernel": per_step_us,
-            "gemv_graph_us": {k: {"us": round(v[0], 2), "GB/s": round(v[1] / v[0] / 1e3, 1)}
-                              for k, v in gemv_us.items()},
+            **more,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(cfg, prompt)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

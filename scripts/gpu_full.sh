@@ -17,9 +17,9 @@ step() {
 }
 [ "${SKIP_TESTS:-0}" = 1 ] || step tests 1000 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 170 --timeout-method thread
 [ "${SKIP_SMOKE:-0}" = 1 ] || step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 900 python bench.py ${BENCH_ARGS:-}
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 900 python bench.py --full ${BENCH_ARGS:-}
 if [ "${SKIP_PROF:-0}" != 1 ]; then
-  step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+  step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
   find "$OUT/prof" -name '*kernel_trace.csv' -delete
   find "$OUT/prof" -name '*.db' -delete
 fi

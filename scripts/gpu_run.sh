@@ -19,9 +19,9 @@ step() {  # name seconds cmd...
 if [ -n "${TESTS:-}" ]; then
   step tests 900 python -u -m pytest $TESTS -m gpu -v -p no:cacheprovider -x --timeout 170 --timeout-method thread
 fi
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 900 python bench.py ${BENCH_ARGS:-}
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 900 python bench.py --full ${BENCH_ARGS:-}
 if [ "${SKIP_PROF:-0}" != 1 ]; then
-  step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline ${PROF_ARGS:-}
+  step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline ${PROF_ARGS:-}
   find "$OUT/prof" -name '*kernel_trace.csv' -delete
   find "$OUT/prof" -name '*.db' -delete
 fi

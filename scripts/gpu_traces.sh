@@ -25,5 +25,5 @@ for v in ${TRACES:-}; do   # e.g. TRACES="bf16 fp8"
   [ -n "$f" ] && python3 scripts/step_gaps.py "$f" 10 ${MARKER:-commit_kernel} > "$OUT/gaps_$v.txt" && cat "$OUT/gaps_$v.txt" | head -20
   find "$OUT/trace_$v" -name '*.csv' -size +5M -delete
 done
-[ "${SKIP_BENCH:-1}" = 1 ] || step bench 900 python bench.py ${BENCH_ARGS:-}
+[ "${SKIP_BENCH:-1}" = 1 ] || step bench 900 python bench.py --full ${BENCH_ARGS:-}
 exit 0

@@ -181,7 +181,7 @@ def covered_keys():
 
 
 def probe_keys():
-    """bench.py's roofline section: mx_llm_bench_gemv sweeps of the qkv / o-proj / gate-up /
+    """``bench.py --full``'s roofline section: mx_llm_bench_gemv sweeps of the qkv / o-proj / gate-up /
     down GEMVs over every layer, one row (capi.hip: the o-proj probe runs without the split
     merge, rows per wave from the rpw_o option, i.e. 1)."""
     from _dispatch import DEFAULTS, EPI_QKV, EPI_RESID, EPI_SILU, gemv_launch
@@ -195,7 +195,7 @@ def probe_keys():
 
 def bench_envelope(prompt_len=10, stream_prompts=(16, 64), job_prompts=(22, 259),
                    max_tokens=1200, batch=32, fp8_batch=8, opts=None):
-    """Every (rows, longest span) a default bench.py run can step, at Orpheus widths:
+    """Every (rows, longest span) a default ``bench.py --full`` run can step, at Orpheus widths:
     configs[1] and the HTTP lines (one bf16 row), configs[2] (<= 32 rows, prompts of 16..64
     ids), configs[3] long_read and its 8-GPU rank share (<= 32 rows, the jobs' 22..259-id
     prompts), configs[4] (<= 8 e4m3 rows and one e4m3 row).  Rows x spans are taken as a
