@@ -68,6 +68,18 @@ typedef struct mx_sampling {
   uint64_t seed;
 } mx_sampling;
 
+/* Optional extras of a stream (mx_llm_prefill_ex); all zero = neutral = mx_llm_prefill.
+ * Order: temperature, then top_k and min_p, then top_p (vLLM's order).  top_k keeps the k most
+ * probable ids (ties at the k-th kept together), min_p the ids with probability >= min_p x the
+ * top probability; the nucleus mass is taken over what they leave.  penalty_last_n = N > 0
+ * applies the repetition penalty to the ids at the last N positions only (prompt included);
+ * 0 = the whole sequence.  N <= 255: the window is kept as byte counts. */
+typedef struct mx_sampling_ext {
+  int32_t top_k;
+  float min_p;
+  int32_t penalty_last_n;
+} mx_sampling_ext;
+
 /* ---- library / memory -------------------------------------------------------------- */
 const char* mx_version(void);
 int mx_host_alloc(size_t bytes, void** host_ptr, void** dev_ptr); /* pinned, device-mapped */
@@ -91,6 +103,11 @@ int mx_llm_finalize(mx_llm* ctx);
  * generation parameters, pick the first token.  Enqueued on `stream`. */
 int mx_llm_prefill(mx_llm* ctx, int slot, int row, const int32_t* ids_host, int n_ids,
                    const mx_sampling* params, void* stream);
+/* The same with the extras (`ext` NULL = neutral).  MX_ERR_ARG on top_k < 0, min_p outside
+ * [0, 1] or NaN, penalty_last_n outside [0, 255].  Every prefill resets the slot's penalty
+ * state, so whole-sequence and windowed requests may follow each other on one slot. */
+int mx_llm_prefill_ex(mx_llm* ctx, int slot, int row, const int32_t* ids_host, int n_ids,
+                      const mx_sampling* params, const mx_sampling_ext* ext, void* stream);
 /* One decode step for rows [0, n_rows), each under its slot's parameters (hipGraph-captured
  * per row count and attention grid; replayed). */
 int mx_llm_decode(mx_llm* ctx, int n_rows, void* stream);
@@ -177,6 +194,11 @@ int32_t* mx_llm_history(mx_llm* ctx);
  * first mx_llm_decode; costs one extra write per vocab entry) and read one row back. */
 int mx_llm_debug_logits(mx_llm* ctx, int enable);
 int mx_llm_read_logits(mx_llm* ctx, int row, float* host_out, void* stream);
+/* Parity/debug, idle context, after a wait: run the sampler of `row`'s slot on caller logits
+ * [vocab] (host) at RNG counter `pos`; nothing is committed (the row's kept logits are
+ * overwritten).  A greedy slot returns the smallest-index maximum. */
+int mx_llm_debug_sample(mx_llm* ctx, int row, const float* logits_host, int pos,
+                        int32_t* token_out, void* stream);
 const char* mx_llm_last_error(const mx_llm* ctx);
 void mx_llm_destroy(mx_llm* ctx);
 

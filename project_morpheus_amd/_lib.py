@@ -51,6 +51,11 @@ class Sampling(C.Structure):
                 ("repetition_penalty", C.c_float), ("seed", C.c_uint64)]
 
 
+class SamplingExt(C.Structure):
+    """mx_sampling_ext: all zero is neutral (no top-k, no min-p, whole-sequence penalty)."""
+    _fields_ = [("top_k", C.c_int32), ("min_p", C.c_float), ("penalty_last_n", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mx_version": (C.c_char_p, []),
@@ -61,6 +66,8 @@ _SIGS = {
     "mx_llm_set_rope": (C.c_int, [_P, _P, _P, C.c_int]),
     "mx_llm_finalize": (C.c_int, [_P]),
     "mx_llm_prefill": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(Sampling), _P]),
+    "mx_llm_prefill_ex": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(Sampling),
+                                    C.POINTER(SamplingExt), _P]),
     "mx_llm_decode": (C.c_int, [_P, C.c_int, _P]),
     "mx_llm_check": (C.c_int, [_P, _P]),
     "mx_llm_decode_profiled": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_double), C.c_int]),
@@ -80,6 +87,7 @@ _SIGS = {
     "mx_llm_history": (C.POINTER(C.c_int32), [_P]),
     "mx_llm_debug_logits": (C.c_int, [_P, C.c_int]),
     "mx_llm_read_logits": (C.c_int, [_P, C.c_int, _P, _P]),
+    "mx_llm_debug_sample": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), _P]),
     "mx_llm_last_error": (C.c_char_p, [_P]),
     "mx_llm_destroy": (None, [_P]),
     "mx_snac_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

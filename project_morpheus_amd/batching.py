@@ -9,7 +9,8 @@ engine, one request per thread (Orpheus-TTS/orpheus_tts_pypi/orpheus_tts/engine_
 * every stream owns one KV slot and one decode row; a step decodes rows [0, n_rows) at once
   (``mx_llm_decode(n_rows)``: one hipGraph per row count, the one-launch step for one row),
   rows without a stream are parked on the scratch slot; each row decodes under its own
-  generation parameters (penalty, temperature, top-p, seed: per-slot state set at prefill);
+  generation parameters (penalty and its window, temperature, top-k, min-p, top-p, seed:
+  per-slot state set at prefill);
 * rows are compacted: when a stream ends, the highest live row moves into the lowest free
   one (``mx_llm_move_row``: same KV slot, stream-ordered between steps), so a step runs the
   row class of the live stream count, not of the highest row index ever used;
@@ -68,6 +69,9 @@ class StreamRequest:
     temperature: float = 0.0                # <= 0: greedy (the parity mode)
     top_p: float = 1.0
     seed: int = 0                           # sampling stream (Philox key)
+    top_k: int = 0                          # 0: no limit
+    min_p: float = 0.0                      # 0: off
+    penalty_last_n: int = 0                 # 0: penalty over the whole sequence; N <= 255
     noise_seed: Optional[int] = None        # SNAC noise stream (None: assigned at admission)
     on_chunk: Optional[Callable[["StreamRequest", bytes], None]] = None
     on_done: Optional[Callable[["StreamRequest"], None]] = None
@@ -99,10 +103,23 @@ class StreamRequest:
         self.cancelled = True
 
 
-def check_params(penalty: float, temperature: float, top_p: float, max_tokens: int) -> None:
-    """Reject generation parameters the device cannot run (mx_llm_prefill returns MX_ERR_ARG
-    for them): a bad request must fail alone, at submit time, never inside the GPU loop."""
+def check_params(penalty: float, temperature: float, top_p: float, max_tokens: int, *,
+                 top_k: Optional[int] = None, min_p: Optional[float] = None,
+                 penalty_last_n: Optional[int] = None) -> None:
+    """Reject generation parameters the device cannot run (mx_llm_prefill_ex returns
+    MX_ERR_ARG for them): a bad request must fail alone, at submit time, never inside the GPU
+    loop."""
     import math
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int)
+                              or not 0 <= top_k < 2 ** 31):
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    if min_p is not None and (isinstance(min_p, bool) or not isinstance(min_p, (int, float))
+                              or not 0 <= min_p <= 1):  # (NaN fails the comparison)
+        raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+    if penalty_last_n is not None and (isinstance(penalty_last_n, bool)
+                                       or not isinstance(penalty_last_n, int)
+                                       or not 0 <= penalty_last_n <= 255):
+        raise ValueError(f"penalty_last_n must be an integer in [0, 255], got {penalty_last_n!r}")
     for name, v in (("repetition_penalty", penalty), ("temperature", temperature),
                     ("top_p", top_p)):
         if not isinstance(v, (int, float)) or not math.isfinite(v):
@@ -291,7 +308,8 @@ class BatchSynthesizer:
         return self
 
     def submit(self, req: StreamRequest) -> StreamHandle:
-        check_params(req.penalty, req.temperature, req.top_p, req.max_tokens)
+        check_params(req.penalty, req.temperature, req.top_p, req.max_tokens, top_k=req.top_k,
+                     min_p=req.min_p, penalty_last_n=req.penalty_last_n)
         if self._thread is None:
             self.start()
         h = StreamHandle(req) if req.audio else TokenHandle(req)
@@ -394,9 +412,13 @@ class BatchSynthesizer:
                 self._admitted += 1
                 slot = min(free_slots)
                 try:  # a request the device rejects fails alone; the loop serves on
-                    check_params(req.penalty, req.temperature, req.top_p, req.max_tokens)
+                    check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
+                                 top_k=req.top_k, min_p=req.min_p,
+                                 penalty_last_n=req.penalty_last_n)
                     llm.prefill(slot, r.idx, req.prompt_ids, req.penalty, self.stream,
-                                temperature=req.temperature, top_p=req.top_p, seed=req.seed)
+                                temperature=req.temperature, top_p=req.top_p, seed=req.seed,
+                                top_k=req.top_k, min_p=req.min_p,
+                                penalty_last_n=req.penalty_last_n)
                 except (ValueError, _lib.MxError) as e:
                     if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
                         raise  # a device failure is not this request's fault

@@ -49,17 +49,40 @@ def sse_event(cid: str, created: int, model: str, text: str, finish: Optional[st
 
 def params_from_payload(p: Dict[str, Any]) -> Dict[str, Any]:
     """Generation parameters of a request; ValueError (HTTP 400) for values the engine
-    cannot run (non-numbers, temperature < 0, top_p outside (0, 1], penalty <= 0)."""
+    cannot run (non-numbers, temperature < 0, top_p outside (0, 1], penalty <= 0, top_k < 0,
+    min_p outside [0, 1], repeat_last_n outside -1 .. 255).  ``top_k``, ``min_p`` and
+    ``repeat_last_n`` (the llama.cpp server's names) are returned only when the payload names
+    them; ``repeat_last_n`` maps to ``penalty_last_n``: -1 the whole sequence (0), 0 the penalty
+    off (``penalty`` 1.0), 1-255 the window."""
     from .batching import check_params
+
+    def whole(v, name):
+        if isinstance(v, bool) or (isinstance(v, float) and not v.is_integer()) or \
+                not isinstance(v, (int, float)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+        return int(v)
     try:
         out = {"max_tokens": int(p.get("max_tokens") or I.MAX_TOKENS),
                "temperature": float(p.get("temperature", I.TEMPERATURE)),
                "top_p": float(p.get("top_p", I.TOP_P)),
                "penalty": float(p.get("repeat_penalty", p.get("repetition_penalty",
                                                               I.REPETITION_PENALTY)))}
+        if "top_k" in p:
+            out["top_k"] = whole(p["top_k"], "top_k")
+        if "min_p" in p:
+            out["min_p"] = float(p["min_p"])
+        if "repeat_last_n" in p:
+            n = whole(p["repeat_last_n"], "repeat_last_n")
+            if not -1 <= n <= 255:
+                raise ValueError(f"repeat_last_n must be in -1 .. 255, got {n}")
+            if n == 0:
+                out["penalty"] = 1.0
+            out["penalty_last_n"] = max(n, 0)
     except (TypeError, ValueError) as e:
         raise ValueError(f"bad generation parameter: {e}") from e
-    check_params(out["penalty"], out["temperature"], out["top_p"], out["max_tokens"])
+    check_params(out["penalty"], out["temperature"], out["top_p"], out["max_tokens"],
+                 top_k=out.get("top_k"), min_p=out.get("min_p"),
+                 penalty_last_n=out.get("penalty_last_n"))
     return out
 
 

@@ -137,6 +137,33 @@ ENGINE_OPTIONS = {k[len("MORPHEUS_MX_OPT_"):]: int(v) for k, v in os.environ.ite
 # adapter descriptor declares, adapter_registry.py:54: n milliseconds of PCM = 48 n bytes).
 PULL_UNIT = os.environ.get("MORPHEUS_MX_PULL_UNIT", "bytes")
 
+# Sampler chain presets (MORPHEUS_MX_SAMPLER): (top_k, min_p, repeat_last_n).  "llama_cpp" holds
+# what a llama.cpp server is believed to add to the posted payload by default; llama.cpp is not
+# in the reference tree, so the three values are unpinned (Sampling).
+SAMPLER_PRESETS = {"": (0, 0.0, 0), "llama_cpp": (40, 0.05, 64)}
+
+
+def sampler_defaults(environ=None):
+    """(TOP_K, MIN_P, REPEAT_LAST_N) defaults of a request that names none of them:
+    MORPHEUS_MX_TOP_K (>= 0; 0 = no limit), MORPHEUS_MX_MIN_P ([0, 1]; 0 = off) and
+    MORPHEUS_MX_REPEAT_LAST_N ([0, 255]; 0 = penalty over the whole sequence), each falling back
+    to the MORPHEUS_MX_SAMPLER preset; all neutral when nothing is set.  A value that does not
+    parse or lies out of range counts as unset."""
+    env = os.environ if environ is None else environ
+    k, p, n = SAMPLER_PRESETS.get(env.get("MORPHEUS_MX_SAMPLER", "").strip().lower(),
+                                  SAMPLER_PRESETS[""])
+
+    def pick(name, cast, ok, default):
+        try:
+            v = cast(env[name])
+        except (KeyError, TypeError, ValueError):
+            return default
+        return v if ok(v) else default
+
+    return (pick("MORPHEUS_MX_TOP_K", int, lambda v: 0 <= v < 2 ** 31, k),
+            pick("MORPHEUS_MX_MIN_P", float, lambda v: 0.0 <= v <= 1.0, p),
+            pick("MORPHEUS_MX_REPEAT_LAST_N", int, lambda v: 0 <= v <= 255, n))
+
 
 def request_seed(prompt_ids, seed=None) -> int:
     """The seed of one request: ``seed`` if given, else content-derived (CONTENT_SEED=1) or a

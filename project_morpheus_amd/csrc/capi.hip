@@ -110,6 +110,12 @@ struct mx_llm {
   // per KV slot sampling state (set at prefill; the scratch slot stays greedy)
   float *penalty = nullptr, *samp_temp = nullptr, *samp_top_p = nullptr;
   uint32_t* samp_seed = nullptr;
+  int32_t* samp_top_k = nullptr;  // per KV slot: 0 = no limit
+  float* samp_min_p = nullptr;    // per KV slot: 0 = off
+  int32_t* last_n = nullptr;      // per KV slot penalty window (0: the whole sequence)
+  int32_t* recent = nullptr;      // [slots][PEN_RING] ids at the window's positions
+  unsigned long long* dbg_best = nullptr;  // mx_llm_debug_sample: its own key and counter
+  int32_t* dbg_pos = nullptr;              // (slot word, position word)
   float* logits = nullptr;      // [max_rows_head][vocab] penalised logits (sampling / parity)
   int logits_all = 0;           // option via mx_llm_debug_logits: keep every row's logits
   int32_t* hist_host = nullptr;
@@ -119,6 +125,7 @@ struct mx_llm {
   std::vector<int> pos_mirror;            // host copy of row_pos (position of next token)
   std::vector<char> row_active;
   std::vector<char> row_samples;          // row's slot samples (temperature > 0): head runs the sampler
+  std::vector<char> row_chain;            // ... with a non-neutral top-k or min-p (sample_chain_kernel)
   std::map<int, hipGraph_t> graph_defs;
   bool final = false;
   int max_rows = 0;
@@ -230,6 +237,7 @@ extern "C" int mx_llm_create(int device, const mx_llm_config* cfg, mx_llm** out)
   x->pos_mirror.assign(c.max_batch, 0);
   x->row_active.assign(c.max_batch, 0);
   x->row_samples.assign(c.max_batch, 0);
+  x->row_chain.assign(c.max_batch, 0);
   x->max_rows = c.max_batch > c.max_prefill ? c.max_batch : c.max_prefill;
   x->nsplit_max = c.max_pos / ATT_S_MIN;
   const int qkv_rows = c.heads * 128 + 2 * c.kv_heads * 128;
@@ -587,6 +595,22 @@ extern "C" int mx_llm_finalize(mx_llm* x) {
     MX_TRY(x, make(x->lm, c.vocab, H, &x->lm_f));
     MX_TRY(x, hipDeviceSynchronize());
   }
+  // sampler-chain state, one block allocated last: every other buffer keeps the address it
+  // has without it (the multi-row GEMM's atomic arrival order is sensitive to placement).
+  // All zero = neutral: no top-k, no min-p, whole-sequence penalty.
+  if (!x->last_n) {
+    const size_t slots = (size_t)x->c.max_slots + 1;
+    const size_t words = (3 + PEN_RING) * slots + 2 + 2;  // ... + dbg_pos[2] + dbg_best (u64)
+    int32_t* blk = nullptr;
+    MX_TRY(x, x->alloc(&blk, words + 1));
+    MX_TRY(x, hipMemset(blk, 0, (words + 1) * 4));
+    x->dbg_best = reinterpret_cast<unsigned long long*>(blk);  // 8-byte aligned: block start
+    x->dbg_pos = blk + 2;
+    x->samp_top_k = blk + 4;
+    x->samp_min_p = reinterpret_cast<float*>(blk + 4 + slots);
+    x->last_n = blk + 4 + 2 * slots;
+    x->recent = blk + 4 + 3 * slots;
+  }
   x->final = true;
   return MX_OK;
 }
@@ -828,12 +852,28 @@ static hipError_t enqueue_layers(mx_llm* x, const RowSet& rs, hipStream_t st, Pr
   return e;
 }
 
+// The sampler node of a step (part of the graph key): none when every row is greedy,
+// sample_kernel, or sample_chain_kernel when a sampling row has a non-neutral top-k / min-p.
+enum { SMP_NONE = 0, SMP_PLAIN = 1, SMP_CHAIN = 2 };
+
+static hipError_t enqueue_sampler(mx_llm* x, const float* lg, const int32_t* slot,
+                                  const int32_t* pos, int R, unsigned long long* best,
+                                  int sampler, hipStream_t st) {
+  SampleChainArgs ca{};
+  SampleArgs& sa = ca.s;
+  sa.logits = lg; sa.row_slot = slot; sa.row_pos = pos; sa.temp = x->samp_temp;
+  sa.top_p = x->samp_top_p; sa.seed = x->samp_seed; sa.best = best; sa.V = x->c.vocab;
+  if (sampler != SMP_CHAIN) return launch_sample(sa, R, st);
+  ca.top_k = x->samp_top_k; ca.min_p = x->samp_min_p;
+  return launch_sample_chain(ca, R, st);
+}
+
 // lm_head + penalty + argmax for R rows, then -- only when one of them samples -- the
 // sampler (greedy rows return at once).  `best` points into x->best; its offset selects the
 // rows of x->logits used.
 static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
                                const int32_t* pos, int R, unsigned long long* best,
-                               bool sample, hipStream_t st) {
+                               int sampler, hipStream_t st) {
   const auto& c = x->c;
   float* lg = x->logits + (size_t)(best - x->best) * c.vocab;
   GemvArgs g{};
@@ -844,11 +884,8 @@ static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
   g.penalty = x->penalty; g.samp_temp = x->samp_temp; g.best = best;
   g.logits = lg; g.logits_all = x->logits_all;
   hipError_t e = launch_gemv(g, EPI_ARGMAX, true, st);
-  if (e != hipSuccess || !sample) return e;  // all-greedy steps carry no sampler node
-  SampleArgs sa{};
-  sa.logits = lg; sa.row_slot = slot; sa.row_pos = pos; sa.temp = x->samp_temp;
-  sa.top_p = x->samp_top_p; sa.seed = x->samp_seed; sa.best = best; sa.V = c.vocab;
-  return launch_sample(sa, R, st);
+  if (e != hipSuccess || sampler == SMP_NONE) return e;  // all-greedy steps carry no sampler node
+  return enqueue_sampler(x, lg, slot, pos, R, best, sampler, st);
 }
 
 // Longest attention span of the next step over rows [0, n_rows) (host mirror of row_pos).
@@ -868,10 +905,11 @@ static int att_nw_of(const mx_llm* x, int R, int max_len) {
   return nw;
 }
 
-static bool any_samples(const mx_llm* x, int n_rows) {
+static int sampler_of(const mx_llm* x, int n_rows) {
+  int s = SMP_NONE;
   for (int r = 0; r < n_rows; ++r)
-    if (x->row_samples[r]) return true;
-  return false;
+    if (x->row_samples[r]) s = std::max(s, x->row_chain[r] ? (int)SMP_CHAIN : (int)SMP_PLAIN);
+  return s;
 }
 
 static EngineArgs engine_args(const mx_llm* x) {
@@ -895,7 +933,7 @@ static EngineArgs engine_args(const mx_llm* x) {
   return a;
 }
 
-static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, bool sample,
+static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, int sampler,
                                  hipStream_t st, Prof* prof) {
   const auto& c = x->c;
   hipError_t e = hipSuccess;
@@ -912,7 +950,7 @@ static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, bo
   }
   PROF_BEGIN(PK_HEAD);
   if (e == hipSuccess)
-    e = enqueue_head(x, x->h_dec, x->row_slot, x->row_pos, n_rows, x->best, sample, st);
+    e = enqueue_head(x, x->h_dec, x->row_slot, x->row_pos, n_rows, x->best, sampler, st);
   PROF_END();
   PROF_BEGIN(PK_COMMIT);
   if (e == hipSuccess) {
@@ -921,6 +959,7 @@ static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, bo
     cm.row_token = x->row_token; cm.seen = x->seen; cm.hist = x->hist_dev; cm.embed = x->embed;
     cm.h = x->h_dec; cm.hidden = c.hidden; cm.vocab = c.vocab; cm.max_pos = c.max_pos;
     cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
+    cm.last_n = x->last_n; cm.recent = x->recent;
     // an engine launch that gave up commits nothing (its history entry reads -1)
     cm.abort_word = (n_rows == 1 && x->b1_engine) ? x->eng_status_d : nullptr;
     e = launch_commit(cm, n_rows, st);
@@ -931,9 +970,21 @@ static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, bo
 
 extern "C" int mx_llm_prefill(mx_llm* x, int slot, int row, const int32_t* ids, int n,
                               const mx_sampling* sp, void* stream) {
+  return mx_llm_prefill_ex(x, slot, row, ids, n, sp, nullptr, stream);
+}
+
+extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* ids, int n,
+                                 const mx_sampling* sp, const mx_sampling_ext* ext,
+                                 void* stream) {
   if (!x || !ids || !sp) return MX_ERR_ARG;
   if (!(sp->repetition_penalty > 0.f) || !(sp->top_p > 0.f) || sp->temperature < 0.f)
     MX_FAIL(x, MX_ERR_ARG, "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0");
+  const mx_sampling_ext neutral{0, 0.f, 0};
+  const mx_sampling_ext& xe = ext ? *ext : neutral;
+  if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
+      xe.penalty_last_n >= PEN_RING)
+    MX_FAIL(x, MX_ERR_ARG,
+            "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255");
   if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
   const auto& c = x->c;
   if (slot < 0 || slot >= c.max_slots || row < 0 || row >= c.max_batch)
@@ -946,18 +997,31 @@ extern "C" int mx_llm_prefill(mx_llm* x, int slot, int row, const int32_t* ids, 
   MX_TRY(x, launch_set_slot_params(x->penalty, x->samp_temp, x->samp_top_p, x->samp_seed, slot,
                                    sp->repetition_penalty, sp->temperature,
                                    sp->top_p < 1.f ? sp->top_p : 1.f, sp->seed, st));
+  const int win = xe.penalty_last_n;
+  // every prefill starts the slot clean: seen flags / window counts here, the ring below
   MX_TRY(x, hipMemsetAsync(x->seen + (size_t)slot * c.vocab, 0, c.vocab, st));
   MX_TRY(x, hipMemcpyAsync(x->pre_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
   MX_TRY(x, launch_set_rows(x->pre_slot, x->pre_pos, n, slot, 0, st));
-  MX_TRY(x, launch_embed_rows(x->pre_ids, n, slot, x->embed, c.hidden, c.vocab, x->seen,
-                              x->h_pre, st));
+  MX_TRY(x, launch_embed_rows(x->pre_ids, n, slot, x->embed, c.hidden, c.vocab,
+                              win > 0 ? nullptr : x->seen, x->h_pre, st));
   RowSet rs{x->h_pre, x->pre_slot, x->pre_pos, n, n, att_cpw_auto(x, n, n),
             att_nw_of(x, n, n), 0, false};
   rs.nsplit = (n + 32 * rs.nw * rs.cpw - 1) / (32 * rs.nw * rs.cpw);
   MX_TRY(x, enqueue_layers(x, rs, st, nullptr));
+  // the extras, the ring and (window mode: the bytes are counts, filled serially, since
+  // embed_rows marks from many blocks) the window are first read by the head and the commit:
+  // set behind the layers, the launches in front of them are the same with and without extras
+  MX_TRY(x, launch_set_slot_ext(x->samp_top_k, x->samp_min_p, x->last_n, slot, xe.top_k,
+                                xe.min_p, win, st));
+  MX_TRY(x, hipMemsetAsync(x->recent + (size_t)slot * PEN_RING, 0, PEN_RING * 4, st));
+  if (win > 0)
+    MX_TRY(x, launch_window_prefill(x->pre_ids, n, win, slot, c.vocab, x->seen, x->recent, st));
   MX_TRY(x, hipMemsetAsync(x->best + row, 0, 8, st));
+  const bool samples = sp->temperature > 0.f;
+  const bool chain = samples && (xe.top_k > 0 || xe.min_p > 0.f);
   MX_TRY(x, enqueue_head(x, x->h_pre + (size_t)(n - 1) * c.hidden, x->pre_slot + (n - 1),
-                         x->pre_pos + (n - 1), 1, x->best + row, sp->temperature > 0.f, st));
+                         x->pre_pos + (n - 1), 1, x->best + row,
+                         chain ? SMP_CHAIN : samples ? SMP_PLAIN : SMP_NONE, st));
   // bind decode row -> slot at position n-1, then commit (advances to n)
   MX_TRY(x, launch_set_rows(x->row_slot + row, x->row_pos + row, 1, slot, n - 1, st));
   CommitArgs cm{};
@@ -965,10 +1029,12 @@ extern "C" int mx_llm_prefill(mx_llm* x, int slot, int row, const int32_t* ids, 
   cm.row_token = x->row_token + row; cm.seen = x->seen; cm.hist = x->hist_dev;
   cm.embed = x->embed; cm.h = x->h_dec + (size_t)row * c.hidden; cm.hidden = c.hidden;
   cm.vocab = c.vocab; cm.max_pos = c.max_pos; cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
+  cm.last_n = x->last_n; cm.recent = x->recent;
   MX_TRY(x, launch_commit(cm, 1, st));
   x->pos_mirror[row] = n;
   x->row_active[row] = 1;
-  x->row_samples[row] = sp->temperature > 0.f ? 1 : 0;
+  x->row_samples[row] = samples ? 1 : 0;
+  x->row_chain[row] = chain ? 1 : 0;
   return MX_OK;
 }
 
@@ -1028,14 +1094,14 @@ extern "C" int mx_llm_decode(mx_llm* x, int n_rows, void* stream) {
   const int S = 32 * cpw * nw;
   const int nsplit = engine ? 0 : (ml + S - 1) / S;
   // (chunks and waves are part of the key: one nsplit can come from several shapes; so is
-  // whether any row samples: all-greedy graphs have no sampler node)
-  const bool sample = any_samples(x, n_rows);
-  const int key = (((n_rows * 16 + cpw) * 16 + nw) * 4096 + nsplit) * 2 + (sample ? 1 : 0);
+  // the sampler node: all-greedy graphs have none, the others sample_kernel or the chain)
+  const int sampler = sampler_of(x, n_rows);
+  const int key = (((n_rows * 16 + cpw) * 16 + nw) * 4096 + nsplit) * 4 + sampler;
   auto it = x->graphs.find(key);
   if (it == x->graphs.end()) {
     MX_TRY(x, hipStreamSynchronize(st));
     MX_TRY(x, hipStreamBeginCapture(x->cap, hipStreamCaptureModeRelaxed));
-    hipError_t e = enqueue_decode(x, n_rows, nsplit * S, cpw, sample, x->cap, nullptr);
+    hipError_t e = enqueue_decode(x, n_rows, nsplit * S, cpw, sampler, x->cap, nullptr);
     hipGraph_t g = nullptr;
     hipError_t e2 = hipStreamEndCapture(x->cap, &g);
     MX_TRY(x, e);
@@ -1060,7 +1126,7 @@ extern "C" int mx_llm_decode_profiled(mx_llm* x, int n_rows, void* stream,
   if (check_room(x, n_rows)) return MX_ERR_STATE;
   Prof prof;
   const int ml = decode_max_len(x, n_rows);
-  hipError_t e = enqueue_decode(x, n_rows, ml, att_cpw_auto(x, n_rows, ml), any_samples(x, n_rows),
+  hipError_t e = enqueue_decode(x, n_rows, ml, att_cpw_auto(x, n_rows, ml), sampler_of(x, n_rows),
                                 st, &prof);
   mirror_step(x, n_rows);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1531,6 +1597,7 @@ extern "C" int mx_llm_release_row(mx_llm* x, int row, void* stream) {
   x->pos_mirror[row] = 0;
   x->row_active[row] = 0;
   x->row_samples[row] = 0;
+  x->row_chain[row] = 0;
   return MX_OK;
 }
 
@@ -1544,9 +1611,11 @@ extern "C" int mx_llm_move_row(mx_llm* x, int dst, int src, void* stream) {
   x->pos_mirror[dst] = x->pos_mirror[src];
   x->row_active[dst] = x->row_active[src];
   x->row_samples[dst] = x->row_samples[src];
+  x->row_chain[dst] = x->row_chain[src];
   x->pos_mirror[src] = 0;
   x->row_active[src] = 0;
   x->row_samples[src] = 0;
+  x->row_chain[src] = 0;
   return MX_OK;
 }
 
@@ -1584,6 +1653,31 @@ extern "C" int mx_llm_read_logits(mx_llm* x, int row, float* host_out, void* str
   MX_TRY(x, hipMemcpyAsync(host_out, x->logits + (size_t)row * x->c.vocab,
                            (size_t)x->c.vocab * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   MX_TRY(x, hipStreamSynchronize((hipStream_t)stream));
+  return MX_OK;
+}
+
+extern "C" int mx_llm_debug_sample(mx_llm* x, int row, const float* logits_host, int pos,
+                                   int32_t* token_out, void* stream) {
+  if (!x || !logits_host || !token_out || row < 0 || row >= x->c.max_batch || pos < 0)
+    return MX_ERR_ARG;
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  if (!x->row_active[row]) MX_FAIL(x, MX_ERR_STATE, "debug_sample: row has no stream");
+  const auto& c = x->c;
+  hipStream_t st = (hipStream_t)stream;
+  MX_TRY(x, hipSetDevice(x->device));
+  // the row's logits buffer is free between steps; the key and the counter are the call's own
+  float* lg = x->logits + (size_t)row * c.vocab;
+  MX_TRY(x, hipMemcpyAsync(lg, logits_host, (size_t)c.vocab * 4, hipMemcpyHostToDevice, st));
+  MX_TRY(x, launch_set_rows(x->dbg_pos, x->dbg_pos + 1, 1, 0, pos, st));
+  if (x->row_samples[row])
+    MX_TRY(x, enqueue_sampler(x, lg, x->row_slot + row, x->dbg_pos + 1, 1, x->dbg_best,
+                              x->row_chain[row] ? SMP_CHAIN : SMP_PLAIN, st));
+  else
+    MX_TRY(x, launch_argmax_row(lg, c.vocab, x->dbg_best, st));
+  unsigned long long key = 0ull;
+  MX_TRY(x, hipMemcpyAsync(&key, x->dbg_best, 8, hipMemcpyDeviceToHost, st));
+  MX_TRY(x, hipStreamSynchronize(st));
+  *token_out = (int32_t)~(uint32_t)(key & 0xffffffffull);  // argmax_index (mx_common.h)
   return MX_OK;
 }
 

@@ -882,12 +882,13 @@ __global__ __launch_bounds__(256) void commit_kernel(CommitArgs a) {
   const int r = blockIdx.x;
   const int dst = a.dst_row ? a.dst_row[r] : r;
   __shared__ int tok_s;
+  int slot = 0, new_pos = -1;  // thread 0: the slot and position of a committed token
   if (threadIdx.x == 0) {
     const unsigned long long key = a.best[r];
     const int tok = (int)argmax_index(key);
     tok_s = tok;
     a.best[r] = 0ull;
-    const int slot = a.row_slot[dst];
+    slot = a.row_slot[dst];
     const bool gave_up = a.abort_word &&
         __hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
     if (gave_up) {  // the step's outputs are invalid: no advance, the history slot reads -1,
@@ -899,12 +900,15 @@ __global__ __launch_bounds__(256) void commit_kernel(CommitArgs a) {
       const int pos = min(a.row_pos[dst] + a.pos_advance, a.max_pos - 1);  // new token
       a.row_pos[dst] = pos;
       a.row_token[dst] = tok;
-      a.seen[(size_t)slot * a.vocab + tok] = 1;
       a.hist[(size_t)slot * a.max_pos + pos] = tok;
+      new_pos = pos;
     }
   }
   __syncthreads();
   const int tok = tok_s;
+  // the slot's window length hangs off the slot load: fetched here, in flight under the
+  // gather, so it adds no dependent load in front of the barrier
+  const int N = new_pos >= 0 ? a.last_n[slot] : 0;
   const uint4* e = reinterpret_cast<const uint4*>(a.embed + (size_t)tok * a.hidden);
   float4* h = reinterpret_cast<float4*>(a.h + (size_t)dst * a.hidden);
   for (int c = threadIdx.x; c < (a.hidden >> 3); c += 256) {
@@ -912,15 +916,51 @@ __global__ __launch_bounds__(256) void commit_kernel(CommitArgs a) {
     h[2 * c] = make_float4(bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y));
     h[2 * c + 1] = make_float4(bf16_lo(w.z), bf16_hi(w.z), bf16_lo(w.w), bf16_hi(w.w));
   }
+  if (new_pos >= 0) {  // thread 0 of a committing row: mark the token seen
+    uint8_t* seen = a.seen + (size_t)slot * a.vocab;
+    if (N > 0) {  // window: the bytes count the ids at positions pos-N+1 .. pos (<= N <= 255)
+      int32_t* ring = a.recent + (size_t)slot * PEN_RING;
+      if (new_pos >= N) --seen[ring[(new_pos - N) & (PEN_RING - 1)]];
+      ++seen[tok];
+      ring[new_pos & (PEN_RING - 1)] = tok;
+    } else {
+      seen[tok] = 1;
+    }
+  }
 }
 
-// Prefill rows: h[r] = embed[ids[r]], seen[slot][ids[r]] = 1.  Grid R, block 256.
+// Window-mode prefill (penalty_last_n = N > 0): the slot's seen bytes and ring, zeroed by the
+// caller, become the counts of the ids at prompt positions max(0, n-N) .. n-1 and those ids
+// at their positions.  One block; thread 0 walks the ids serially (a byte count has no
+// atomic, and N <= 255).
+__global__ __launch_bounds__(64) void window_prefill_kernel(const int32_t* ids, int n, int N,
+                                                            int slot, int vocab, uint8_t* seen,
+                                                            int32_t* recent) {
+  if (threadIdx.x != 0) return;
+  int32_t* ring = recent + (size_t)slot * PEN_RING;
+  uint8_t* cnt = seen + (size_t)slot * vocab;
+  for (int p = max(0, n - N); p < n; ++p) {
+    const int tok = ids[p];
+    ++cnt[tok];
+    ring[p & (PEN_RING - 1)] = tok;
+  }
+}
+
+hipError_t launch_window_prefill(const int32_t* ids, int n, int N, int slot, int vocab,
+                                 uint8_t* seen, int32_t* recent, hipStream_t st) {
+  hipLaunchKernelGGL(window_prefill_kernel, dim3(1), dim3(64), 0, st, ids, n, N, slot,
+                     vocab, seen, recent);
+  return hipGetLastError();
+}
+
+// Prefill rows: h[r] = embed[ids[r]], seen[slot][ids[r]] = 1 (no `seen`: window mode, the
+// counts come from window_prefill_kernel).  Grid R, block 256.
 __global__ __launch_bounds__(256) void embed_rows_kernel(const int32_t* ids, int slot,
                                                          const uint16_t* embed, int hidden,
                                                          int vocab, uint8_t* seen, float* h) {
   const int r = blockIdx.x;
   const int tok = ids[r];
-  if (threadIdx.x == 0) seen[(size_t)slot * vocab + tok] = 1;
+  if (seen && threadIdx.x == 0) seen[(size_t)slot * vocab + tok] = 1;
   const uint4* e = reinterpret_cast<const uint4*>(embed + (size_t)tok * hidden);
   float4* out = reinterpret_cast<float4*>(h + (size_t)r * hidden);
   for (int c = threadIdx.x; c < (hidden >> 3); c += 256) {

@@ -116,7 +116,12 @@ struct CommitArgs {
   int scratch_slot;          // rows bound to this slot are parked: no advance, no history
   const int* abort_word;     // null, or the persistent engine's host-mapped status: when set,
                              // nothing is committed and the history entry reads -1
+  // penalty window (last_n[slot] = N > 0): the slot's seen bytes are counts of the ids at the
+  // last N positions, recent[slot] is the ring of those ids (cell = position & 255)
+  const int32_t* last_n;     // [slots]
+  int32_t* recent;           // [slots][PEN_RING]
 };
+constexpr int PEN_RING = 256;  // ring cells per slot: the window is at most PEN_RING - 1 ids
 
 
 hipError_t gemv_prepare(int kmax);
@@ -142,9 +147,24 @@ struct SampleArgs {
   int V;
 };
 hipError_t launch_sample(const SampleArgs& a, int R, hipStream_t st);
+// the sampler with the top-k / min-p filters in front of the nucleus (sample_chain_kernel)
+struct SampleChainArgs {
+  SampleArgs s;
+  const int32_t* top_k;    // per KV slot: 0 = no limit
+  const float* min_p;      // per KV slot: 0 = off
+};
+hipError_t launch_sample_chain(const SampleChainArgs& a, int R, hipStream_t st);
+// best[0] = argmax key of logits[0, V) (smallest index among equal maxima)
+hipError_t launch_argmax_row(const float* logits, int V, unsigned long long* best,
+                             hipStream_t st);
 hipError_t launch_set_slot_params(float* penalty, float* temp, float* top_p, uint32_t* seed,
                                   int slot, float pen, float t, float p, uint64_t s,
                                   hipStream_t st);
+hipError_t launch_set_slot_ext(int32_t* top_k, float* min_p, int32_t* last_n, int slot, int k,
+                               float mp, int n, hipStream_t st);
+// window mode prefill: counts and ring of the last min(n, N) prompt ids (one block, serial)
+hipError_t launch_window_prefill(const int32_t* ids, int n, int N, int slot, int vocab,
+                                 uint8_t* seen, int32_t* recent, hipStream_t st);
 hipError_t launch_set_rows(int32_t* slot, int32_t* pos, int n, int slot_val, int pos0,
                            hipStream_t st);
 hipError_t launch_set_scalar(float* p, float v, hipStream_t st);

@@ -202,6 +202,216 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
   }
 }
 
+// The sampler with two filters in front of the nucleus (temperature, then top-k and min-p,
+// then top-p: vLLM's order).  Token i is in the filter set F iff f_i > 0, e_i >= min_p and
+// #{j : e_j > e_i} < top_k (0: no limit; ties at the k-th value kept together).  F is an upper
+// set in e-order, so both filters are ONE threshold `fbits` on the bit pattern of e: min_p
+// gives its bits directly, top-k the same 12 + 12 + 8 radix select run over counts (find_cut
+// unchanged, thr = k).  The mass select and the race of sample_kernel then run with everything
+// below fbits masked out, so Z is the mass of F.  A row whose slot has neutral extras does no
+// extra sweep and computes exactly what sample_kernel computes (fbits = 0); a row with top-k
+// takes three more sweeps, one with min-p alone none.
+__global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) {
+  const SampleArgs& a = c.s;
+  const int r = blockIdx.x;
+  const int slot = a.row_slot[r];
+  const float T = a.temp[slot];
+  if (!(T > 0.f)) return;  // greedy row: the epilogue's argmax key stands
+  const float top_p = a.top_p[slot];
+  const int top_k = c.top_k[slot];
+  const float min_p = c.min_p[slot];
+  const uint32_t k0 = a.seed[2 * slot], k1 = a.seed[2 * slot + 1];
+  const uint32_t ctr1 = (uint32_t)a.row_pos[r];
+  const float* lg = a.logits + (size_t)r * a.V;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int V = a.V;
+
+  __shared__ unsigned long long hist[4096];
+  __shared__ unsigned long long wsum[SMP_T / 64];
+  __shared__ float fred[SMP_T / 64];
+  __shared__ int cut_bin;
+  __shared__ unsigned long long cut_base;
+
+  // pass 1: max logit
+  float m = -INFINITY;
+  for (int i = t; i < V; i += SMP_T) m = fmaxf(m, lg[i]);
+  m = wave_max(m);
+  if (lane == 0) fred[w] = m;
+  for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
+  __syncthreads();
+  m = fred[0];
+  for (int i = 1; i < SMP_T / 64; ++i) m = fmaxf(m, fred[i]);
+  auto e_of = [&](int i) { return expf((lg[i] - m) / T); };
+  auto f_of = [&](float e) { return (unsigned long long)(e * SMP_FX); };
+
+  // the filter threshold: min_p's bits (positive floats order as their bit patterns) ...
+  uint32_t fbits = min_p > 0.f ? __float_as_uint(min_p) : 0u;
+  // ... and, for 0 < top_k < V, the k-th largest e among the tokens with f > 0
+  if (top_k > 0 && top_k < V) {
+    // count pass 1: how many tokens have f > 0, and their histogram over bits 31..20 of e
+    unsigned long long n = 0ull;
+    for (int i = t; i < V; i += SMP_T) {
+      const float e = e_of(i);
+      if (f_of(e)) {
+        ++n;
+        atomicAdd(&hist[__float_as_uint(e) >> 20], 1ull);
+      }
+    }
+    n = u64_wave_sum(n);
+    if (lane == 0) wsum[w] = n;
+    __syncthreads();
+    unsigned long long npos = 0ull;
+    for (int i = 0; i < SMP_T / 64; ++i) npos += wsum[i];
+    // (npos >= 1: the maximum has e = 1.)  k past the last such token keeps them all.
+    const unsigned long long kthr = (unsigned long long)top_k < npos ? (unsigned long long)top_k : npos;
+    __syncthreads();  // every thread has read wsum
+    find_cut<1>(hist, 0ull, kthr, &cut_bin, &cut_base, wsum);
+    const uint32_t kb1 = (uint32_t)cut_bin;
+    const unsigned long long kc1 = cut_base;
+
+    // count pass 2: bits 19..8 inside bin kb1
+    for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
+    __syncthreads();
+    for (int i = t; i < V; i += SMP_T) {
+      const float e = e_of(i);
+      const uint32_t bits = __float_as_uint(e);
+      if ((bits >> 20) == kb1 && f_of(e)) atomicAdd(&hist[(bits >> 8) & 0xFFFu], 1ull);
+    }
+    __syncthreads();
+    find_cut<4>(hist, kc1, kthr, &cut_bin, &cut_base, wsum);
+    const uint32_t kb12 = (kb1 << 12) | (uint32_t)cut_bin;
+    const unsigned long long kc2 = cut_base;
+
+    // count pass 3: bits 7..0 inside (kb1, kb2)
+    for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
+    __syncthreads();
+    for (int i = t; i < V; i += SMP_T) {
+      const float e = e_of(i);
+      const uint32_t bits = __float_as_uint(e);
+      if ((bits >> 8) == kb12 && f_of(e)) atomicAdd(&hist[bits & 0xFFu], 1ull);
+    }
+    __syncthreads();
+    find_cut<1>(hist, kc2, kthr, &cut_bin, &cut_base, wsum);
+    const uint32_t kcut = (kb12 << 8) | (uint32_t)cut_bin;
+    fbits = kcut > fbits ? kcut : fbits;
+    __syncthreads();  // every thread has read cut_bin
+    for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
+    __syncthreads();
+  }
+
+  // mass pass 1: Z over F and the first radix histogram (bits 31..20 of e)
+  unsigned long long z = 0ull;
+  for (int i = t; i < V; i += SMP_T) {
+    const float e = e_of(i);
+    const uint32_t bits = __float_as_uint(e);
+    const unsigned long long f = bits >= fbits ? f_of(e) : 0ull;
+    z += f;
+    if (f) atomicAdd(&hist[bits >> 20], f);
+  }
+  z = u64_wave_sum(z);
+  if (lane == 0) wsum[w] = z;
+  __syncthreads();
+  unsigned long long Z = 0ull;
+  for (int i = 0; i < SMP_T / 64; ++i) Z += wsum[i];
+  unsigned long long thr = Z;
+  if (top_p < 1.f) {
+    thr = (unsigned long long)((double)Z * (double)top_p);
+    if (thr < 1ull) thr = 1ull;
+  }
+  __syncthreads();  // every thread has read wsum
+  find_cut<1>(hist, 0ull, thr, &cut_bin, &cut_base, wsum);
+  const uint32_t b1 = (uint32_t)cut_bin;
+  const unsigned long long c1 = cut_base;
+
+  // mass pass 2: bits 19..8 inside bin b1
+  for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
+  __syncthreads();
+  for (int i = t; i < V; i += SMP_T) {
+    const float e = e_of(i);
+    const uint32_t bits = __float_as_uint(e);
+    if ((bits >> 20) == b1 && bits >= fbits) {
+      const unsigned long long f = f_of(e);
+      if (f) atomicAdd(&hist[(bits >> 8) & 0xFFFu], f);
+    }
+  }
+  __syncthreads();
+  find_cut<4>(hist, c1, thr, &cut_bin, &cut_base, wsum);
+  const uint32_t b12 = (b1 << 12) | (uint32_t)cut_bin;
+  const unsigned long long c2 = cut_base;
+
+  // mass pass 3: bits 7..0 inside (b1, b2)
+  for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
+  __syncthreads();
+  for (int i = t; i < V; i += SMP_T) {
+    const float e = e_of(i);
+    const uint32_t bits = __float_as_uint(e);
+    if ((bits >> 8) == b12 && bits >= fbits) {
+      const unsigned long long f = f_of(e);
+      if (f) atomicAdd(&hist[bits & 0xFFu], f);
+    }
+  }
+  __syncthreads();
+  find_cut<1>(hist, c2, thr, &cut_bin, &cut_base, wsum);
+  // (the cut bin holds mass, so tcut is the e of a token in F: tcut >= fbits)
+  const uint32_t tcut = (b12 << 8) | (uint32_t)cut_bin;
+
+  // race pass: exponential race over the kept tokens
+  unsigned long long best = 0ull;
+  for (int i = t; i < V; i += SMP_T) {
+    const float e = e_of(i);
+    if (__float_as_uint(e) >= tcut) {
+      const uint32_t x = philox_x0((uint32_t)i, ctr1, k0, k1);
+      const float u = ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23, u < 1 exactly
+      const float s = e / -logf(u);
+      const unsigned long long key = argmax_key(s, (uint32_t)i);
+      best = key > best ? key : best;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(best, d, MX_WAVE);
+    best = o > best ? o : best;
+  }
+  if (lane == 0) wsum[w] = best;
+  __syncthreads();
+  if (t == 0) {
+    unsigned long long k = wsum[0];
+    for (int i = 1; i < SMP_T / 64; ++i) k = wsum[i] > k ? wsum[i] : k;
+    a.best[r] = k;
+  }
+}
+
+// Argmax key of one row of caller logits (the greedy branch of mx_llm_debug_sample).
+__global__ __launch_bounds__(SMP_T) void argmax_row_kernel(const float* lg, int V,
+                                                          unsigned long long* out) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  __shared__ unsigned long long wbest[SMP_T / 64];
+  unsigned long long best = 0ull;
+  for (int i = t; i < V; i += SMP_T) {
+    const unsigned long long key = argmax_key(lg[i], (uint32_t)i);
+    best = key > best ? key : best;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(best, d, MX_WAVE);
+    best = o > best ? o : best;
+  }
+  if (lane == 0) wbest[w] = best;
+  __syncthreads();
+  if (t == 0) {
+    unsigned long long k = wbest[0];
+    for (int i = 1; i < SMP_T / 64; ++i) k = wbest[i] > k ? wbest[i] : k;
+    out[0] = k;
+  }
+}
+
+__global__ void set_slot_ext_kernel(int32_t* top_k, float* min_p, int32_t* last_n, int slot,
+                                    int k, float mp, int n) {
+  top_k[slot] = k;
+  min_p[slot] = mp;
+  last_n[slot] = n;
+}
+
 __global__ void set_slot_params_kernel(float* penalty, float* temp, float* top_p,
                                        uint32_t* seed, int slot, float pen, float t, float p,
                                        uint32_t s0, uint32_t s1) {
@@ -214,6 +424,24 @@ __global__ void set_slot_params_kernel(float* penalty, float* temp, float* top_p
 
 hipError_t launch_sample(const SampleArgs& a, int R, hipStream_t st) {
   hipLaunchKernelGGL(sample_kernel, dim3(R), dim3(SMP_T), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sample_chain(const SampleChainArgs& a, int R, hipStream_t st) {
+  hipLaunchKernelGGL(sample_chain_kernel, dim3(R), dim3(SMP_T), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_argmax_row(const float* logits, int V, unsigned long long* best,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(argmax_row_kernel, dim3(1), dim3(SMP_T), 0, st, logits, V, best);
+  return hipGetLastError();
+}
+
+hipError_t launch_set_slot_ext(int32_t* top_k, float* min_p, int32_t* last_n, int slot, int k,
+                               float mp, int n, hipStream_t st) {
+  hipLaunchKernelGGL(set_slot_ext_kernel, dim3(1), dim3(1), 0, st, top_k, min_p, last_n, slot,
+                     k, mp, n);
   return hipGetLastError();
 }
 

@@ -83,14 +83,20 @@ class LlmEngine:
         _lib.check(rc, self.lib.mx_llm_last_error, self.h)
 
     def prefill(self, slot: int, row: int, ids: Sequence[int], penalty: float, stream, *,
-                temperature: float = 0.0, top_p: float = 1.0, seed: int = 0) -> None:
+                temperature: float = 0.0, top_p: float = 1.0, seed: int = 0,
+                top_k: int = 0, min_p: float = 0.0, penalty_last_n: int = 0) -> None:
         """Prefill ``ids`` into KV ``slot`` bound to decode ``row``; the slot decodes under
-        (penalty, temperature, top_p, seed) until the next prefill (temperature 0 = greedy)."""
+        (penalty, temperature, top_p, seed) until the next prefill (temperature 0 = greedy).
+        ``top_k`` / ``min_p`` filter before the nucleus (0 = off); ``penalty_last_n`` = N > 0
+        penalises the ids of the last N positions only (0 = the whole sequence, N <= 255)."""
         arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
         sp = _lib.Sampling(temperature=float(temperature), top_p=float(top_p),
                            repetition_penalty=float(penalty), seed=int(seed) & (2**64 - 1))
-        self._check(self.lib.mx_llm_prefill(self.h, slot, row, arr.ctypes.data, len(arr),
-                                            C.byref(sp), C.c_void_p(stream.cuda_stream)))
+        ext = _lib.SamplingExt(top_k=int(top_k), min_p=float(min_p),
+                               penalty_last_n=int(penalty_last_n))
+        self._check(self.lib.mx_llm_prefill_ex(self.h, slot, row, arr.ctypes.data, len(arr),
+                                               C.byref(sp), C.byref(ext),
+                                               C.c_void_p(stream.cuda_stream)))
 
     def decode(self, n_rows: int, stream) -> None:
         """One step for rows [0, n_rows), each under its slot's generation parameters."""
@@ -171,6 +177,19 @@ class LlmEngine:
         self._check(self.lib.mx_llm_read_logits(self.h, row, out.ctypes.data,
                                                 C.c_void_p(stream.cuda_stream)))
         return out
+
+    def debug_sample(self, row: int, logits, pos: int, stream=None) -> int:
+        """Parity/debug, idle engine: the token the sampler of ``row``'s slot draws from
+        caller ``logits`` [vocab] at RNG counter ``pos``; nothing is committed."""
+        lg = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+        if lg.shape != (self.cfg.vocab,):
+            raise ValueError(f"logits must have shape ({self.cfg.vocab},)")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        tok = C.c_int32(-1)
+        self._check(self.lib.mx_llm_debug_sample(self.h, row, lg.ctypes.data, int(pos),
+                                                 C.byref(tok), C.c_void_p(stream.cuda_stream)))
+        return tok.value
 
     def row_state(self, row: int):
         """(active, next position) of decode row ``row`` (host view)."""
@@ -314,7 +333,8 @@ class Synthesizer:
             stop_ids: Sequence[int] = STOP_IDS, inject_ids: Optional[Sequence[int]] = None,
             stats: Optional[UtteranceStats] = None, slot: int = 0, row: int = 0,
             temperature: float = 0.0, top_p: float = 1.0, seed: int = 0,
-            noise_seed: Optional[int] = None) -> Iterator[bytes]:
+            noise_seed: Optional[int] = None, top_k: int = 0, min_p: float = 0.0,
+            penalty_last_n: int = 0) -> Iterator[bytes]:
         """Prefill, then decode up to ``max_tokens`` tokens (engine_class.py:103-134), greedy
         unless ``temperature`` > 0.  Window j's SNAC noise is drawn from (noise_seed, j).
 
@@ -331,7 +351,8 @@ class Synthesizer:
         stop = set(int(s) for s in stop_ids)
 
         llm.prefill(slot, row, prompt_ids, penalty, self.stream, temperature=temperature,
-                    top_p=top_p, seed=seed)
+                    top_p=top_p, seed=seed, top_k=top_k, min_p=min_p,
+                    penalty_last_n=penalty_last_n)
         ev = torch.cuda.Event()
         ev.record(self.stream)
         inflight.append((0, ev))

@@ -3,7 +3,8 @@
 Mirrors Morpheus_Client/tts_engine/inference.py (same names and semantics):
   * ``MAX_TOKENS/TEMPERATURE/TOP_P`` from ``ORPHEUS_*`` env (:75-90),
     ``update_generation_params`` (:93-102), ``REPETITION_PENALTY = 1.1`` (:105),
-    ``SAMPLE_RATE`` (:108);
+    ``SAMPLE_RATE`` (:108); ``TOP_K/MIN_P/REPEAT_LAST_N`` are this engine's own (the
+    reference leaves them to its engines' defaults): ``MORPHEUS_MX_*`` env, neutral when unset;
   * voice lists and ``DEFAULT_VOICE`` (:125-159);
   * ``START_TOKEN_ID`` / ``END_TOKEN_IDS`` (:166-167), ``format_prompt`` string form (:209-223);
   * id form of the prompt, ``OrpheusModel._format_prompt`` (engine_class.py:77-98);
@@ -19,6 +20,8 @@ from typing import Iterable, List, Sequence
 
 import numpy as np
 
+from .config import sampler_defaults
+
 
 def _env(name, default, cast):
     try:
@@ -32,10 +35,19 @@ TEMPERATURE = _env("ORPHEUS_TEMPERATURE", "0.6", float)
 TOP_P = _env("ORPHEUS_TOP_P", "0.9", float)
 REPETITION_PENALTY = 1.1
 SAMPLE_RATE = _env("ORPHEUS_SAMPLE_RATE", "24000", int)
+# sampler chain extras (0 / 0.0 / 0 = off; REPEAT_LAST_N counts positions, 0 = whole sequence)
+TOP_K, MIN_P, REPEAT_LAST_N = sampler_defaults()
 
 
-def update_generation_params(*, temperature=None, top_p=None, max_tokens=None) -> None:
-    global TEMPERATURE, TOP_P, MAX_TOKENS
+def update_generation_params(*, temperature=None, top_p=None, max_tokens=None, top_k=None,
+                             min_p=None, repeat_last_n=None) -> None:
+    global TEMPERATURE, TOP_P, MAX_TOKENS, TOP_K, MIN_P, REPEAT_LAST_N
+    if top_k is not None:
+        TOP_K = int(top_k)
+    if min_p is not None:
+        MIN_P = float(min_p)
+    if repeat_last_n is not None:
+        REPEAT_LAST_N = int(repeat_last_n)
     if temperature is not None:
         TEMPERATURE = float(temperature)
     if top_p is not None:

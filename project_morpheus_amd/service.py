@@ -84,7 +84,8 @@ class Service:
     def submit(self, text: str, voice: str = I.DEFAULT_VOICE, max_tokens: Optional[int] = None,
                penalty: float = I.REPETITION_PENALTY, temperature: Optional[float] = None,
                top_p: Optional[float] = None, seed: Optional[int] = None,
-               prompt_ids=None) -> StreamHandle:
+               prompt_ids=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+               penalty_last_n: Optional[int] = None) -> StreamHandle:
         """Queue one utterance on this GPU's batch loop (non-blocking)."""
         ids = list(prompt_ids) if prompt_ids is not None else self.prompt_ids(text, voice)
         max_tokens = max_tokens or I.MAX_TOKENS
@@ -96,6 +97,9 @@ class Service:
             prompt_ids=ids, max_tokens=max_tokens, penalty=penalty,
             temperature=I.TEMPERATURE if temperature is None else temperature,
             top_p=I.TOP_P if top_p is None else top_p, seed=key, noise_seed=key,
+            top_k=I.TOP_K if top_k is None else top_k,
+            min_p=I.MIN_P if min_p is None else min_p,
+            penalty_last_n=I.REPEAT_LAST_N if penalty_last_n is None else penalty_last_n,
             inject_ids=C.synthetic_audio_ids(max_tokens, seed=key)
             if self.synthetic_audio else None)
         if self.synthetic_audio:
@@ -104,14 +108,20 @@ class Service:
 
     def submit_tokens(self, prompt_ids, max_tokens: Optional[int] = None,
                       temperature: Optional[float] = None, top_p: Optional[float] = None,
-                      penalty: float = I.REPETITION_PENALTY, seed: Optional[int] = None):
+                      penalty: float = I.REPETITION_PENALTY, seed: Optional[int] = None,
+                      top_k: Optional[int] = None, min_p: Optional[float] = None,
+                      penalty_last_n: Optional[int] = None):
         """Token-only stream (completions surface): a TokenHandle of generated ids."""
         ids = list(prompt_ids)
         key = C.request_seed(ids, seed)
         req = StreamRequest(prompt_ids=ids, max_tokens=max_tokens or I.MAX_TOKENS,
                             penalty=penalty,
                             temperature=I.TEMPERATURE if temperature is None else temperature,
-                            top_p=I.TOP_P if top_p is None else top_p, seed=key, audio=False)
+                            top_p=I.TOP_P if top_p is None else top_p, seed=key, audio=False,
+                            top_k=I.TOP_K if top_k is None else top_k,
+                            min_p=I.MIN_P if min_p is None else min_p,
+                            penalty_last_n=I.REPEAT_LAST_N if penalty_last_n is None
+                            else penalty_last_n)
         return self.batch.submit(req)
 
     def stream(self, text: str, voice: str = I.DEFAULT_VOICE, max_tokens: Optional[int] = None,
