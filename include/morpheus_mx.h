@@ -142,7 +142,11 @@ int mx_llm_decode_profiled(mx_llm* ctx, int n_rows, void* stream, double* ms_by_
  * "engine_timeout" (bound of every engine wait, 100 MHz ticks; 0 = 50 ms), "engine_dbg" (timing
  * experiments: 1 = no hand-off waits, 2 = no weight stream; outputs invalid), "bench_one_layer"
  * (diagnostic: the GEMV probes below sweep layer 0 only, its weights resident on die).  Drops
- * the captured graphs so the next mx_llm_decode re-captures with the new choice. */
+ * the captured graphs so the next mx_llm_decode re-captures with the new choice.
+ * One key is a test hook rather than a knob: "debug_poison_att_partials" = 1 fills the attention
+ * split partials (m, l, accumulators) with 0xFF bytes -- quiet NaNs -- once, on the call (it
+ * waits for the device before and after, keeps the captured graphs, and is part of no step):
+ * the steps after it must not let a split slot past the row's live count into their result. */
 int mx_llm_set_option(mx_llm* ctx, const char* key, int value);
 /* Diagnostic (option engine_trace on): after a device sync, copy the last engine launch's
  * timeline, 12 stamps of the 100 MHz clock per (CU, layer) -- consumer: layer start, input

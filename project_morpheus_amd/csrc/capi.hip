@@ -1437,7 +1437,21 @@ extern "C" int mx_llm_bench_gemv_trace(mx_llm* x, int which, int n_rows, uint64_
 extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
   if (!x || !key) return MX_ERR_ARG;
   const std::string k(key);
-  if (k == "legacy_gemv") {
+  if (k == "debug_poison_att_partials") {
+    // test hook, not a knob and not part of any step: on the call, every attention split
+    // partial becomes 0xFF bytes (quiet NaNs), so a consumer that lets a dead split slot into
+    // its result shows.  Waits for the device on both sides; the captured graphs stay.
+    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "debug_poison_att_partials must be 0 or 1");
+    if (value) {
+      const size_t part_rows = (size_t)x->max_rows * (x->c.max_pos / ATT_S_MIN);
+      MX_TRY(x, hipSetDevice(x->device));
+      MX_TRY(x, hipDeviceSynchronize());
+      MX_TRY(x, hipMemset(x->part_ml, 0xFF, part_rows * x->c.heads * 2 * sizeof(float)));
+      MX_TRY(x, hipMemset(x->part_acc, 0xFF, part_rows * x->c.heads * 128 * sizeof(float)));
+      MX_TRY(x, hipDeviceSynchronize());
+    }
+    return MX_OK;
+  } else if (k == "legacy_gemv") {
     x->legacy_gemv = value;
   } else if (k == "rows_head_mt") {
     if (value != 1 && value != 2) MX_FAIL(x, MX_ERR_ARG, "rows_head_mt must be 1 or 2");

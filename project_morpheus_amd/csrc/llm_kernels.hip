@@ -244,8 +244,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
 //   go first, then every weight load of the wave (RPW*KCH x 16 B per lane, non-temporal),
 //   and only then the prologue (norm, LDS staging) runs, under the weight loads' latency.
 //   All loads are unconditional (addresses clamped), so hipcc can count vmcnt exactly.
-//   Epilogue operands that do not depend on the result (residual, RoPE row) are fetched
-//   with the activation.
+//   The residual and the e4m3 row scales are fetched with the activation.  The EPI_QKV
+//   epilogue reads its kernel arguments, row_slot[0] / row_pos[0] and the RoPE factors after
+//   the reduction, in lane 0 (three dependent round trips at the tail): issuing them behind the
+//   weight loads measured slower twice (profiles/r04_qkv_rope_prefetch_not_kept.log).
 // ---------------------------------------------------------------------------------
 // F8: weights are OCP e4m3 bytes with one fp32 scale per row (16 weights per 16-byte load,
 // converted in registers by v_cvt_pk_f32_fp8 -- exact), else bf16 (8 per load).
@@ -254,27 +256,38 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
 // att = sum_s e^(m_s - M) acc_s / sum_s e^(m_s - M) l_s over the row's live splits (at most
 // NSM).  The partial loads go out first, the weight loads behind them, and the merge runs
 // under the weight latency -- the split merge costs no extra launch, ticket or round trip.
+// The loads do not wait for the row's position either: all NSM slots of a group are read at
+// addresses fixed by the kernel arguments (slot s, clamped to the host's bound att_nsm on the
+// row's splits and to the att_stride slots a kv head owns; slots past the bound re-read the
+// last one, which costs no second fetch), row_pos[0] is requested beside them, and
+// merge_apply drops the slots at or past the live count with selects on the loaded values --
+// a dead slot may hold anything (never written, a stale partial, NaN, Inf) and none of it
+// reaches M, den or num.
 template <int NSM>
 struct MergeIn {  // one 8-dim group's split partials, loaded
   float2 ml[NSM];
   float4 lo[NSM], hi[NSM];
 };
 template <int NSM>
-__device__ __forceinline__ void merge_load(const GemvArgs& a, int j, int ns, MergeIn<NSM>& in) {
+__device__ __forceinline__ void merge_load(const GemvArgs& a, int stride, int nb, int j, MergeIn<NSM>& in) {
   const int GRP = a.heads / a.kv_heads;
   const int hh = j >> 4, d0 = (j & 15) * 8;
   const int kvh = hh / GRP, hin = hh - kvh * GRP;
-  const size_t pb = (size_t)kvh * a.att_stride;
+  // slot s of this kv head sits s * GRP (m, l) pairs / accumulator rows past slot 0: the lane's
+  // part of the address is formed once, the slot's part is wave-uniform
+  const size_t p0 = (size_t)kvh * stride * GRP + hin;
+  const float* ml0 = a.att_ml + p0 * 2;
+  const float* ac0 = a.att_acc + p0 * 128 + d0;
 #pragma unroll
   for (int s = 0; s < NSM; ++s) {
-    const size_t sp = pb + min(s, ns - 1);
-    in.ml[s] = *reinterpret_cast<const float2*>(a.att_ml + (sp * GRP + hin) * 2);
-    const float4* ac = reinterpret_cast<const float4*>(a.att_acc + (sp * GRP + hin) * 128 + d0);
+    const size_t so = (size_t)(min(s, nb - 1) * GRP);
+    in.ml[s] = *reinterpret_cast<const float2*>(ml0 + so * 2);
+    const float4* ac = reinterpret_cast<const float4*>(ac0 + so * 128);
     in.lo[s] = ac[0];
     in.hi[s] = ac[1];
   }
 }
-template <int NSM>
+template <int NSM, bool EARLY>
 __device__ __forceinline__ void merge_apply(const MergeIn<NSM>& in, int ns, float* x) {
   float M = -INFINITY;
 #pragma unroll
@@ -284,12 +297,17 @@ __device__ __forceinline__ void merge_apply(const MergeIn<NSM>& in, int ns, floa
   float num[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < NSM; ++s) {
+    // a dead slot enters as f = 0 times zeros (selects, not 0 * x: x may be NaN / Inf)
+    const bool live = !EARLY || s < ns;  // (!EARLY: a dead slot is a copy of the last live one)
     const float f = s < ns ? expf(in.ml[s].x - M) : 0.f;
-    den = fmaf(f, in.ml[s].y, den);
-    num[0] = fmaf(f, in.lo[s].x, num[0]); num[1] = fmaf(f, in.lo[s].y, num[1]);
-    num[2] = fmaf(f, in.lo[s].z, num[2]); num[3] = fmaf(f, in.lo[s].w, num[3]);
-    num[4] = fmaf(f, in.hi[s].x, num[4]); num[5] = fmaf(f, in.hi[s].y, num[5]);
-    num[6] = fmaf(f, in.hi[s].z, num[6]); num[7] = fmaf(f, in.hi[s].w, num[7]);
+    const float l = live ? in.ml[s].y : 0.f;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 lo = live ? in.lo[s] : z, hi = live ? in.hi[s] : z;
+    den = fmaf(f, l, den);
+    num[0] = fmaf(f, lo.x, num[0]); num[1] = fmaf(f, lo.y, num[1]);
+    num[2] = fmaf(f, lo.z, num[2]); num[3] = fmaf(f, lo.w, num[3]);
+    num[4] = fmaf(f, hi.x, num[4]); num[5] = fmaf(f, hi.y, num[5]);
+    num[6] = fmaf(f, hi.z, num[6]); num[7] = fmaf(f, hi.w, num[7]);
   }
   const float inv = 1.0f / den;
 #pragma unroll
@@ -305,6 +323,16 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
   constexpr int XPT = (KC + NT - 1) / NT;      // activation chunks per thread
   __shared__ __attribute__((aligned(16))) float4 xs[PL * KC];  // plane q at [q * KC + m]
   __shared__ float red[WPB];
+  // (MRG: read with the first batch of kernel arguments, so that none is fetched between the
+  // request for row_pos[0] and the partial loads)
+  // (the 8-slot merge keeps the dependent order: hoisted, it measured 0.15 us slower per launch
+  // where the 2- and 4-slot merges gained 0.15 - 0.19)
+  constexpr bool MRG_EARLY = NSM > 0 && NSM <= 4;
+  int att_S = a.att_S, att_stride = a.att_stride, att_nb = a.att_nsm;
+  if constexpr (MRG_EARLY) {
+    asm volatile("" : "+s"(att_S), "+s"(att_stride), "+s"(att_nb) : "s"(a.heads), "s"(a.kv_heads));
+    att_nb = max(1, min(att_nb, att_stride));  // slots the loads may touch
+  }
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int G = a.N / RPW;
   int g = blockIdx.x * WPB + wid;
@@ -320,9 +348,12 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
   int ns = 1;
   MergeIn<(NSM > 0 ? NSM : 1)> mi;
   if constexpr (NSM > 0) {
-    const int L = a.row_pos[0] + 1;
-    ns = (L + a.att_S - 1) / a.att_S;
-    merge_load<NSM>(a, min(tid, NG - 1), ns, mi);  // group tid's partial loads go first
+    ns = a.row_pos[0];
+    if constexpr (!MRG_EARLY) {  // the addresses wait for the live count, as the mask does
+      ns = (ns + att_S) / att_S;
+      att_nb = ns;
+    }  // (else: requested here, waited for behind the weights)
+    merge_load<NSM>(a, att_stride, att_nb, min(tid, NG - 1), mi);  // the partial loads go first
   } else {
 #pragma unroll
     for (int i = 0; i < XPT; ++i) {
@@ -350,15 +381,19 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
   for (int r = 0; r < RPW; ++r)
 #pragma unroll
     for (int c = 0; c < KCH; ++c) w[r][c] = load_nt(wp + (size_t)r * KC + c * 64);
+  if constexpr (MRG_EARLY) {  // live splits of the row (the wait for row_pos[0] sits here)
+    const int L = __builtin_amdgcn_readfirstlane(ns) + 1;
+    ns = (L + att_S - 1) / att_S;
+  }
   __builtin_amdgcn_sched_barrier(0);
 
   // 3. prologue under the weight latency
   if constexpr (NSM > 0) {
     // merged 8-dim group j -> chunk m = 8j / EPC, planes q0, q0 + 1 of the staged layout
     for (int j = tid; j < NG; j += NT) {
-      if (j != tid) merge_load<NSM>(a, j, ns, mi);
+      if (j != tid) merge_load<NSM>(a, att_stride, att_nb, j, mi);
       float xm[8];
-      merge_apply<NSM>(mi, ns, xm);
+      merge_apply<NSM, MRG_EARLY>(mi, ns, xm);
       const int m = (8 * j) / EPC, q0 = ((8 * j) % EPC) / 4;
       xs[q0 * KC + m] = make_float4(xm[0], xm[1], xm[2], xm[3]);
       xs[(q0 + 1) * KC + m] = make_float4(xm[4], xm[5], xm[6], xm[7]);
@@ -533,17 +568,42 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
   constexpr int NT = NW * 64;
   constexpr int KM = (GRP * 128 + NT - 1) / NT;  // (head, dim) outputs per thread in merges
   const int split = blockIdx.x, kvh = blockIdx.y, r = blockIdx.z;
-  const int L = a.row_pos[r] + 1;
-  const int nsplit = (L + S - 1) / S;
-  if (split >= nsplit) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
-  const int slot = a.row_slot[r];
-  const size_t head = (size_t)slot * a.kv_heads + kvh;
+  // Two dependent scalar round trips in front of the first K / V load: the kernel arguments
+  // the loads need in one batch (the empty asm holds them in scalar registers from here on;
+  // global-typed, so the loads behind it stay global_load), then the row's position and slot
+  // together.  The Q loads (not the qkv_parts path) depend on neither and go out in between.
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(1))) const u32x4 gu4;
+  typedef __attribute__((address_space(1))) const f32x4 gf4;
+  int L = a.row_pos[r] + 1;
+  int slot = a.row_slot[r];
+  const float* Qa = a.Q;
+  gu4 *Ka = (gu4*)a.kcache, *Va = (gu4*)a.vcache;
+  int heads = a.heads, kv_heads = a.kv_heads, max_pos = a.max_pos;
+  const float* qkv_parts = a.qkv_parts;
+  asm volatile("" : "+s"(Qa), "+s"(Ka), "+s"(Va), "+s"(heads), "+s"(kv_heads), "+s"(max_pos),
+               "+s"(qkv_parts));
+  const bool parts = qkv_parts != nullptr;
+  float4 qlo[4], qhi[4];
+  if (!parts) {
+    const int hq = c < GRP ? c : 0;
+    gf4* qb = (gf4*)(Qa + ((size_t)r * heads + kvh * GRP + hq) * 128 + 8 * g);
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      qlo[st] = __builtin_bit_cast(float4, qb[8 * st]);
+      qhi[st] = __builtin_bit_cast(float4, qb[8 * st + 1]);
+    }
+  }
+  asm volatile("" : "+s"(L), "+s"(slot));
+  const int nsplit = (L + S - 1) / S;
+  if (split >= nsplit) return;
+  const size_t head = (size_t)slot * kv_heads + kvh;
   // K and V in fragment-major 32-position chunks (mx_common.h kv_k_off / kv_v_off): every
   // fragment load below is one lane-linear 1 KB run
-  const uint4* Kf = reinterpret_cast<const uint4*>(a.kcache) + head * a.max_pos * 16;
-  const uint4* Vf = reinterpret_cast<const uint4*>(a.vcache) + head * a.max_pos * 16;
+  gu4* Kf = Ka + head * max_pos * 16;
+  gu4* Vf = Va + head * max_pos * 16;
 
   // K fragments (A operand): tile T, MFMA row rr -> position 8(rr>>2) + 4T + (rr&3);
   // V fragments (B operand): lane (dim 16 t + c, group g) <- positions base + 8g .. +8.
@@ -551,21 +611,21 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
   // masked to -inf below, so their P is exactly 0.
   uint4 kf[2][2][4], vf[2][8];
   auto load_kv = [&](int base, int b) {
-    const uint4* kc = Kf + (size_t)(base >> 5) * 512 + lane;
-    const uint4* vc = Vf + (size_t)(base >> 5) * 512 + lane;
+    gu4* kc = Kf + (size_t)(base >> 5) * 512 + lane;
+    gu4* vc = Vf + (size_t)(base >> 5) * 512 + lane;
 #pragma unroll
     for (int T = 0; T < 2; ++T)
 #pragma unroll
-      for (int st = 0; st < 4; ++st) kf[b][T][st] = kc[(T * 4 + st) * 64];
+      for (int st = 0; st < 4; ++st) kf[b][T][st] = __builtin_bit_cast(uint4, kc[(T * 4 + st) * 64]);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) vf[b][t] = vc[t * 64];
+    for (int t = 0; t < 8; ++t) vf[b][t] = __builtin_bit_cast(uint4, vc[t * 64]);
   };
   // chunks are dealt round-robin over the waves (wave w: chunks w, w + NW, ...), so a split
   // longer than the context still keeps every wave busy with ~equal work
   const int base0 = split * S + wid * 32;
   // (qkv_parts: the wave whose first chunk holds the new position loads it only after it has
   // appended that position, below)
-  const bool late0 = a.qkv_parts != nullptr && base0 == ((L - 1) & ~31);
+  const bool late0 = parts && base0 == ((L - 1) & ~31);
   if (base0 < L && !late0) load_kv(base0, 0);
 
   // Multi-row decode after the seam-free qkv GEMM (AttnArgs::qkv_parts): q, k and v of the new
@@ -576,7 +636,6 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
   // chunk holding it computes that position's k / v and appends them to the cache itself, so
   // its own later loads of those addresses are ordered after the stores (one wave: program
   // order); if that chunk is its first one, its early load above was skipped (late0).
-  const bool parts = a.qkv_parts != nullptr;
   __shared__ __attribute__((aligned(16))) float qs[GRP][128];
   if (parts) {
     const int N = a.qkv_n, NQ = a.heads * 128, KVD = a.kv_heads * 128, R = gridDim.z;
@@ -639,7 +698,6 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
   bf16x8 qf[3][4];
   {
     const int hq = c < GRP ? c : 0;
-    const float* qb = a.Q + ((size_t)r * a.heads + kvh * GRP + hq) * 128 + 8 * g;
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
       float x[8];
@@ -651,8 +709,8 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
         lo = make_float4(l4[0], l4[1], l4[2], l4[3]);
         hi = make_float4(h4[0], h4[1], h4[2], h4[3]);
       } else {
-        lo = *reinterpret_cast<const float4*>(qb + 32 * st);
-        hi = *reinterpret_cast<const float4*>(qb + 32 * st + 4);
+        lo = qlo[st];
+        hi = qhi[st];
       }
       x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w;
       x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
