@@ -80,6 +80,18 @@ typedef struct mx_sampling_ext {
   int32_t penalty_last_n;
 } mx_sampling_ext;
 
+/* Code grammar of a context (mx_llm_set_grammar; DESIGN.md §3 "Code grammar").  The token a
+ * constrained slot puts at position p has phase k = (p - origin) mod phases, origin = the length
+ * of the slot's prefill, and may only be an id of
+ *   A(k) = [code_base + k*codes + code_min, code_base + (k+1)*codes), plus stop_id when k == 0
+ * (stop_id < 0: no stop id).  Every other id behaves as a logit of -inf, in front of the
+ * repetition penalty, temperature, top-k / min-p, top-p and the draw.  Orpheus:
+ * (128266, 4096, 7, 1, 128258) -- seven SNAC code ranges, code 0 excluded (the reference
+ * pipeline drops it, speechpipe.py:146-189), end-of-speech on frame boundaries only. */
+typedef struct mx_code_grammar {
+  int32_t code_base, codes, phases, code_min, stop_id;
+} mx_code_grammar;
+
 /* ---- library / memory -------------------------------------------------------------- */
 const char* mx_version(void);
 int mx_host_alloc(size_t bytes, void** host_ptr, void** dev_ptr); /* pinned, device-mapped */
@@ -131,7 +143,9 @@ int mx_llm_decode_profiled(mx_llm* ctx, int n_rows, void* stream, double* ms_by_
  * attention may take 192-position splits on 6-wave blocks past L 1,024), "att_nw6" (multi-row
  * attention may pick 6-wave blocks: the shortest split covering the context), "gemv_balance"
  * (one-row qkv / merging o-proj: the waves per block that load the most loaded CU least), "rows_frag",
- * "rows_merge", "rows_head_mt", "rows_head_target", "rows_target", "rows_target_qkv", "rows_target_o",
+ * "rows_merge", "rows_head_mt", "rows_head_target", "grammar_head" (steps whose active rows are
+ * all constrained run the lm_head over the grammar's row window only: 1, the default; 0 = always
+ * the whole vocabulary with the mask), "rows_target", "rows_target_qkv", "rows_target_o",
  * "rows_target_gu", "rows_target_down" (the target for one kind of layer launch), "rows_nt_max", "rows_nt1",
  * "rows_pw", "rows_pw_f8", "rows_lds_pad", "rows_atomic" (o-proj / down at >= 2 rows: K ranges
  * add into the residual with float atomics, no split-K seam), "rows_qkv_parts" (decode at >= 2
@@ -181,6 +195,23 @@ int mx_llm_bench_gemv_streams(mx_llm* ctx, int which, int n_rows, int reps, int 
  * (0 = product kernel).  Clobbers decode-row state: only on an idle context. */
 int mx_llm_bench_attention(mx_llm* ctx, int L, int n_rows, int cpw, int debug, int reps,
                            float* us_out);
+/* Set (or, with NULL, clear) the context's code grammar.  After finalize, on an idle context:
+ * MX_ERR_STATE while any row is active.  MX_ERR_ARG on phases < 1, codes < 1, code_min outside
+ * [0, codes), code_base < 0, code_base + phases*codes > vocab, a stop_id inside a code range or
+ * >= vocab.  Clears every slot's flag and drops the captured graphs. */
+int mx_llm_set_grammar(mx_llm* ctx, const mx_code_grammar* grammar);
+/* Debug view of the grammar's row window: the lm_head of a step whose active rows are all
+ * constrained covers ids [*lo, *lo + *n) only (*n = 0: no grammar, or no window fits this
+ * vocabulary and every step runs the whole head with the mask).  *heads = lm_head launches
+ * issued over the window since mx_llm_set_grammar; a launch captured into a step graph counts
+ * once, at capture, not per replay. */
+int mx_llm_grammar_window(const mx_llm* ctx, int* lo, int* n, long long* heads);
+/* Constrain (on != 0) or free the streams `slot` starts from its next prefill on; holds until
+ * changed.  Host state only.  MX_ERR_STATE if turned on without a context grammar.  A step whose
+ * active rows are all constrained computes only the lm_head rows a grammar can allow (option
+ * grammar_head); mx_llm_read_logits of a constrained row returns -inf outside its allowed set,
+ * and mx_llm_debug_sample uses the allowed set of the token that would take position pos + 1. */
+int mx_llm_set_slot_grammar(mx_llm* ctx, int slot, int on);
 /* Park decode row `row` on the scratch slot (stream ended / barge-in reset). */
 int mx_llm_release_row(mx_llm* ctx, int row, void* stream);
 /* Row compaction (stream-ordered on `stream`, between steps): the stream bound to row `src`

@@ -56,6 +56,12 @@ class SamplingExt(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("min_p", C.c_float), ("penalty_last_n", C.c_int32)]
 
 
+class CodeGrammar(C.Structure):
+    """mx_code_grammar: ids [code_base + k*codes + code_min, code_base + (k+1)*codes) at phase k,
+    plus stop_id at phase 0."""
+    _fields_ = [(n, C.c_int32) for n in ("code_base", "codes", "phases", "code_min", "stop_id")]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mx_version": (C.c_char_p, []),
@@ -81,6 +87,10 @@ _SIGS = {
                                     C.POINTER(C.c_double)]),
     "mx_llm_bench_attention": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_float)]),
+    "mx_llm_set_grammar": (C.c_int, [_P, C.POINTER(CodeGrammar)]),
+    "mx_llm_set_slot_grammar": (C.c_int, [_P, C.c_int, C.c_int]),
+    "mx_llm_grammar_window": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_longlong)]),
     "mx_llm_release_row": (C.c_int, [_P, C.c_int, _P]),
     "mx_llm_move_row": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "mx_llm_row_state": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

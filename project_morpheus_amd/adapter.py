@@ -34,12 +34,14 @@ _END = object()
 
 
 def _default_source(prompt: str, voice: str, use_batching: bool, max_batch_chars: int,
-                    cancel: threading.Event) -> Iterator[bytes]:
+                    cancel: threading.Event, grammar: Optional[bool] = None) -> Iterator[bytes]:
     """Every long-form part is submitted at once (they decode as concurrent rows of the
-    GPU's batch) and their PCM is yielded in part order."""
+    GPU's batch) and their PCM is yielded in part order.  ``grammar``: the parts decode under
+    the Orpheus code grammar (None: the service's default, MORPHEUS_MX_GRAMMAR)."""
     from .service import get_service
     svc = get_service()
-    handles = [svc.submit(part, voice) for part in
+    kw = {} if grammar is None else {"grammar": bool(grammar)}
+    handles = [svc.submit(part, voice, **kw) for part in
                I.batch_sentences(prompt, max_batch_chars, use_batching)]
     try:
         for h in handles:
@@ -63,8 +65,10 @@ class MxTTSAdapter:
     source: Callable[..., Iterator[bytes]] = staticmethod(_default_source)
 
     def __init__(self, prompt: str, voice: str = I.DEFAULT_VOICE, *, use_batching: bool = False,
-                 max_batch_chars: int = 1000, pull_unit: Optional[str] = None) -> None:
-        """``pull_unit``: "bytes" (the reference contract, default) or "ms" (the unit the
+                 max_batch_chars: int = 1000, pull_unit: Optional[str] = None,
+                 grammar: Optional[bool] = None) -> None:
+        """``grammar``: decode under the Orpheus code grammar (None: MORPHEUS_MX_GRAMMAR).
+        ``pull_unit``: "bytes" (the reference contract, default) or "ms" (the unit the
         descriptor declares: ``pull(n)`` returns n ms of PCM); default from
         ``config.PULL_UNIT`` (MORPHEUS_MX_PULL_UNIT)."""
         from .config import PULL_UNIT
@@ -72,6 +76,7 @@ class MxTTSAdapter:
         self.voice = voice
         self.use_batching = use_batching
         self.max_batch_chars = max_batch_chars
+        self.grammar = grammar
         unit = pull_unit or PULL_UNIT
         if unit not in ("bytes", "ms"):
             raise ValueError(f"pull_unit must be 'bytes' or 'ms', got {unit!r}")
@@ -88,8 +93,10 @@ class MxTTSAdapter:
             return
         q: queue.Queue = queue.Queue(maxsize=64)
         cancel = threading.Event()
+        # (an injected source keeps the five-argument form unless a grammar choice was made)
+        kw = {} if self.grammar is None else {"grammar": self.grammar}
         src = self.source(self.prompt, self.voice, self.use_batching, self.max_batch_chars,
-                          cancel)
+                          cancel, **kw)
 
         def put(item) -> bool:
             while not cancel.is_set():

@@ -46,7 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import BATCH_DEPTH, SNAC_MAX_HOLD, SNAC_MIN_BATCH, STOP_IDS
+from .config import BATCH_DEPTH, ORPHEUS_GRAMMAR, SNAC_MAX_HOLD, SNAC_MIN_BATCH, STOP_IDS
 from .engine import SAMPLES_PER_FRAME, SLICE_HI, SLICE_LO, LlmEngine, SnacDecoder
 from .schedule import WindowScheduler, code_of_id, frames_for_slice
 
@@ -72,6 +72,7 @@ class StreamRequest:
     top_k: int = 0                          # 0: no limit
     min_p: float = 0.0                      # 0: off
     penalty_last_n: int = 0                 # 0: penalty over the whole sequence; N <= 255
+    grammar: bool = False                   # decode under the Orpheus code grammar
     noise_seed: Optional[int] = None        # SNAC noise stream (None: assigned at admission)
     on_chunk: Optional[Callable[["StreamRequest", bytes], None]] = None
     on_done: Optional[Callable[["StreamRequest"], None]] = None
@@ -407,6 +408,22 @@ class BatchSynthesizer:
                                            f"{llm.max_prefill}, max_pos {llm.max_pos})")
                     complete(req)
                     continue
+                if req.grammar and llm.grammar is None:
+                    # the context takes its grammar while idle: the first constrained request
+                    # waits for the live streams (and, first in line, holds later arrivals)
+                    if any(q.req is not None for q in rows):
+                        waiting.appendleft(req)
+                        return
+                    for q in rows:
+                        park(q)
+                    try:  # a vocabulary that cannot hold the preset fails this request alone
+                        llm.set_grammar(ORPHEUS_GRAMMAR)
+                    except _lib.MxError as e:
+                        if e.rc != _lib.MX_ERR_ARG:
+                            raise
+                        req.error = e
+                        complete(req)
+                        continue
                 if req.noise_seed is None:
                     req.noise_seed = (self.seed * 1000003 + self._admitted) & _MASK48
                 self._admitted += 1
@@ -418,7 +435,7 @@ class BatchSynthesizer:
                     llm.prefill(slot, r.idx, req.prompt_ids, req.penalty, self.stream,
                                 temperature=req.temperature, top_p=req.top_p, seed=req.seed,
                                 top_k=req.top_k, min_p=req.min_p,
-                                penalty_last_n=req.penalty_last_n)
+                                penalty_last_n=req.penalty_last_n, grammar=bool(req.grammar))
                 except (ValueError, _lib.MxError) as e:
                     if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
                         raise  # a device failure is not this request's fault

@@ -53,7 +53,9 @@ def params_from_payload(p: Dict[str, Any]) -> Dict[str, Any]:
     min_p outside [0, 1], repeat_last_n outside -1 .. 255).  ``top_k``, ``min_p`` and
     ``repeat_last_n`` (the llama.cpp server's names) are returned only when the payload names
     them; ``repeat_last_n`` maps to ``penalty_last_n``: -1 the whole sequence (0), 0 the penalty
-    off (``penalty`` 1.0), 1-255 the window."""
+    off (``penalty`` 1.0), 1-255 the window.  ``code_grammar`` (true / false; anything else is
+    an error) is returned as ``grammar`` when the payload names it: the stream then picks from
+    the Orpheus code grammar's allowed ids only."""
     from .batching import check_params
 
     def whole(v, name):
@@ -78,6 +80,10 @@ def params_from_payload(p: Dict[str, Any]) -> Dict[str, Any]:
             if n == 0:
                 out["penalty"] = 1.0
             out["penalty_last_n"] = max(n, 0)
+        if "code_grammar" in p:
+            if not isinstance(p["code_grammar"], bool):
+                raise ValueError(f"code_grammar must be true or false, got {p['code_grammar']!r}")
+            out["grammar"] = p["code_grammar"]
     except (TypeError, ValueError) as e:
         raise ValueError(f"bad generation parameter: {e}") from e
     check_params(out["penalty"], out["temperature"], out["top_p"], out["max_tokens"],

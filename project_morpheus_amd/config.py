@@ -165,6 +165,39 @@ def sampler_defaults(environ=None):
             pick("MORPHEUS_MX_REPEAT_LAST_N", int, lambda v: 0 <= v <= 255, n))
 
 
+@dataclass(frozen=True)
+class CodeGrammar:
+    """mx_code_grammar: the token a constrained stream generates at index i has phase
+    k = i % phases and may only be one of ``allowed(k)`` (Code grammar)."""
+    code_base: int
+    codes: int
+    phases: int
+    code_min: int
+    stop_id: int
+
+    def allowed(self, phase: int):
+        """(range of code ids, stop id or None) of a token of this phase."""
+        lo = self.code_base + phase * self.codes
+        stop = self.stop_id if phase == 0 and self.stop_id >= 0 else None
+        return range(lo + self.code_min, lo + self.codes), stop
+
+    def allows(self, phase: int, tok: int) -> bool:
+        ids, stop = self.allowed(phase)
+        return tok in ids or (stop is not None and tok == stop)
+
+
+# Orpheus speech: seven ranges of 4,096 SNAC codes, code 0 excluded (the reference pipeline
+# drops it and shifts the phase, speechpipe.py:146-189), end-of-speech on frame boundaries only.
+ORPHEUS_GRAMMAR = CodeGrammar(AUDIO_CODE_BASE, 4096, 7, 1, END_OF_SPEECH)
+
+
+def grammar_default(environ=None) -> bool:
+    """Whether a request that does not say is decoded under the code grammar:
+    MORPHEUS_MX_GRAMMAR=1 (also true / yes / on); unset, or anything else, means off."""
+    env = os.environ if environ is None else environ
+    return str(env.get("MORPHEUS_MX_GRAMMAR", "")).strip().lower() in ("1", "true", "yes", "on")
+
+
 def request_seed(prompt_ids, seed=None) -> int:
     """The seed of one request: ``seed`` if given, else content-derived (CONTENT_SEED=1) or a
     fresh random 64-bit value."""

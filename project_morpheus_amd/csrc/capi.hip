@@ -127,6 +127,15 @@ struct mx_llm {
   std::vector<char> row_samples;          // row's slot samples (temperature > 0): head runs the sampler
   std::vector<char> row_chain;            // ... with a non-neutral top-k or min-p (sample_chain_kernel)
   std::map<int, hipGraph_t> graph_defs;
+  // code grammar (mx_llm_set_grammar): constrained slots pick from their phase's ids only
+  bool gram_on = false;
+  mx_code_grammar gram{};
+  int32_t* gram_origin = nullptr;         // device, per KV slot: the prefill's length, or -1
+  std::vector<char> slot_grammar;         // mx_llm_set_slot_grammar: read by the slot's next prefill
+  std::vector<int> row_origin;            // per decode row: its stream's origin, -1 = unconstrained
+  int grammar_head = 1;                   // option: steps of constrained rows only run the lm_head
+  int win_lo = 0, win_n = 0;              //   over ids [win_lo, win_lo + win_n) (win_n 0: no window fits)
+  long long win_heads = 0;                //   lm_head launches issued over it (mx_llm_grammar_window)
   bool final = false;
   int max_rows = 0;
   int legacy_gemv = 0;          // option: grid-stride GEMV for R = 1 too (A/B timing)
@@ -212,6 +221,8 @@ struct mx_llm {
   }
 };
 
+static void drop_graphs(mx_llm* x);
+
 extern "C" int mx_llm_create(int device, const mx_llm_config* cfg, mx_llm** out) {
   if (!cfg || !out) return MX_ERR_ARG;
   auto* x = new mx_llm();
@@ -238,6 +249,8 @@ extern "C" int mx_llm_create(int device, const mx_llm_config* cfg, mx_llm** out)
   x->row_active.assign(c.max_batch, 0);
   x->row_samples.assign(c.max_batch, 0);
   x->row_chain.assign(c.max_batch, 0);
+  x->row_origin.assign(c.max_batch, -1);
+  x->slot_grammar.assign(c.max_slots, 0);
   x->max_rows = c.max_batch > c.max_prefill ? c.max_batch : c.max_prefill;
   x->nsplit_max = c.max_pos / ATT_S_MIN;
   const int qkv_rows = c.heads * 128 + 2 * c.kv_heads * 128;
@@ -852,6 +865,15 @@ static hipError_t enqueue_layers(mx_llm* x, const RowSet& rs, hipStream_t st, Pr
   return e;
 }
 
+static GrammarArgs grammar_args(const mx_llm* x) {
+  GrammarArgs g{};
+  if (x->gram_on) {
+    g.origin = x->gram_origin; g.base = x->gram.code_base; g.codes = x->gram.codes;
+    g.phases = x->gram.phases; g.cmin = x->gram.code_min; g.stop = x->gram.stop_id;
+  }
+  return g;
+}
+
 // The sampler node of a step (part of the graph key): none when every row is greedy,
 // sample_kernel, or sample_chain_kernel when a sampling row has a non-neutral top-k / min-p.
 enum { SMP_NONE = 0, SMP_PLAIN = 1, SMP_CHAIN = 2 };
@@ -863,6 +885,7 @@ static hipError_t enqueue_sampler(mx_llm* x, const float* lg, const int32_t* slo
   SampleArgs& sa = ca.s;
   sa.logits = lg; sa.row_slot = slot; sa.row_pos = pos; sa.temp = x->samp_temp;
   sa.top_p = x->samp_top_p; sa.seed = x->samp_seed; sa.best = best; sa.V = x->c.vocab;
+  sa.gram = grammar_args(x);
   if (sampler != SMP_CHAIN) return launch_sample(sa, R, st);
   ca.top_k = x->samp_top_k; ca.min_p = x->samp_min_p;
   return launch_sample_chain(ca, R, st);
@@ -871,9 +894,11 @@ static hipError_t enqueue_sampler(mx_llm* x, const float* lg, const int32_t* slo
 // lm_head + penalty + argmax for R rows, then -- only when one of them samples -- the
 // sampler (greedy rows return at once).  `best` points into x->best; its offset selects the
 // rows of x->logits used.
+// `window`: every row of the launch that commits is constrained, so only the ids a grammar can
+// allow are computed (x->win_lo, x->win_n); otherwise the whole vocabulary, constrained rows masked.
 static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
                                const int32_t* pos, int R, unsigned long long* best,
-                               int sampler, hipStream_t st) {
+                               int sampler, bool window, hipStream_t st) {
   const auto& c = x->c;
   float* lg = x->logits + (size_t)(best - x->best) * c.vocab;
   GemvArgs g{};
@@ -883,6 +908,15 @@ static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
   g.xstride = c.hidden; g.norm_w = x->norm; g.row_slot = slot; g.seen = x->seen;
   g.penalty = x->penalty; g.samp_temp = x->samp_temp; g.best = best;
   g.logits = lg; g.logits_all = x->logits_all;
+  g.V = c.vocab; g.row_pos = pos; g.gram = grammar_args(x);
+  if (window) {
+    // row-major weights and scales by pointer; the fragment-major copy by tile offset
+    g.id0 = x->win_lo; g.N = x->win_n;
+    g.W = (const uint8_t*)x->lm + (size_t)x->win_lo * c.hidden * x->esz;
+    if (g.wscale) g.wscale += x->win_lo;
+    g.wf_t0 = x->win_lo / 16; g.wf_T = (c.vocab + 15) / 16;
+    ++x->win_heads;
+  }
   hipError_t e = launch_gemv(g, EPI_ARGMAX, true, st);
   if (e != hipSuccess || sampler == SMP_NONE) return e;  // all-greedy steps carry no sampler node
   return enqueue_sampler(x, lg, slot, pos, R, best, sampler, st);
@@ -903,6 +937,19 @@ static int att_nw_of(const mx_llm* x, int R, int max_len) {
   else
     att_batch_shape(x, R, max_len, &nw, &cpw);
   return nw;
+}
+
+// A step runs the lm_head over the grammar's row window when every active row is constrained
+// (parked rows commit nothing and do not count).
+static bool window_of(const mx_llm* x, int n_rows) {
+  if (!x->gram_on || !x->grammar_head || x->win_n <= 0) return false;
+  bool any = false;
+  for (int r = 0; r < n_rows; ++r)
+    if (x->row_active[r]) {
+      if (x->row_origin[r] < 0) return false;
+      any = true;
+    }
+  return any;
 }
 
 static int sampler_of(const mx_llm* x, int n_rows) {
@@ -934,7 +981,7 @@ static EngineArgs engine_args(const mx_llm* x) {
 }
 
 static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, int sampler,
-                                 hipStream_t st, Prof* prof) {
+                                 bool window, hipStream_t st, Prof* prof) {
   const auto& c = x->c;
   hipError_t e = hipSuccess;
   if (n_rows == 1 && x->b1_engine) {  // every layer in one persistent launch
@@ -950,7 +997,7 @@ static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, in
   }
   PROF_BEGIN(PK_HEAD);
   if (e == hipSuccess)
-    e = enqueue_head(x, x->h_dec, x->row_slot, x->row_pos, n_rows, x->best, sampler, st);
+    e = enqueue_head(x, x->h_dec, x->row_slot, x->row_pos, n_rows, x->best, sampler, window, st);
   PROF_END();
   PROF_BEGIN(PK_COMMIT);
   if (e == hipSuccess) {
@@ -1016,12 +1063,16 @@ extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* id
   MX_TRY(x, hipMemsetAsync(x->recent + (size_t)slot * PEN_RING, 0, PEN_RING * 4, st));
   if (win > 0)
     MX_TRY(x, launch_window_prefill(x->pre_ids, n, win, slot, c.vocab, x->seen, x->recent, st));
+  // a constrained slot counts its phases from the prompt's end (-1: unconstrained)
+  const int origin = x->gram_on && x->slot_grammar[slot] ? n : -1;
+  if (x->gram_on) MX_TRY(x, launch_set_slot_origin(x->gram_origin, slot, origin, st));
   MX_TRY(x, hipMemsetAsync(x->best + row, 0, 8, st));
   const bool samples = sp->temperature > 0.f;
   const bool chain = samples && (xe.top_k > 0 || xe.min_p > 0.f);
   MX_TRY(x, enqueue_head(x, x->h_pre + (size_t)(n - 1) * c.hidden, x->pre_slot + (n - 1),
                          x->pre_pos + (n - 1), 1, x->best + row,
-                         chain ? SMP_CHAIN : samples ? SMP_PLAIN : SMP_NONE, st));
+                         chain ? SMP_CHAIN : samples ? SMP_PLAIN : SMP_NONE,
+                         origin >= 0 && x->grammar_head && x->win_n > 0, st));
   // bind decode row -> slot at position n-1, then commit (advances to n)
   MX_TRY(x, launch_set_rows(x->row_slot + row, x->row_pos + row, 1, slot, n - 1, st));
   CommitArgs cm{};
@@ -1035,6 +1086,7 @@ extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* id
   x->row_active[row] = 1;
   x->row_samples[row] = samples ? 1 : 0;
   x->row_chain[row] = chain ? 1 : 0;
+  x->row_origin[row] = origin;
   return MX_OK;
 }
 
@@ -1095,13 +1147,15 @@ extern "C" int mx_llm_decode(mx_llm* x, int n_rows, void* stream) {
   const int nsplit = engine ? 0 : (ml + S - 1) / S;
   // (chunks and waves are part of the key: one nsplit can come from several shapes; so is
   // the sampler node: all-greedy graphs have none, the others sample_kernel or the chain)
+  // ... and whether the lm_head runs over the grammar's row window
   const int sampler = sampler_of(x, n_rows);
-  const int key = (((n_rows * 16 + cpw) * 16 + nw) * 4096 + nsplit) * 4 + sampler;
+  const bool window = window_of(x, n_rows);
+  const int key = ((((n_rows * 16 + cpw) * 16 + nw) * 4096 + nsplit) * 4 + sampler) * 2 + (window ? 1 : 0);
   auto it = x->graphs.find(key);
   if (it == x->graphs.end()) {
     MX_TRY(x, hipStreamSynchronize(st));
     MX_TRY(x, hipStreamBeginCapture(x->cap, hipStreamCaptureModeRelaxed));
-    hipError_t e = enqueue_decode(x, n_rows, nsplit * S, cpw, sampler, x->cap, nullptr);
+    hipError_t e = enqueue_decode(x, n_rows, nsplit * S, cpw, sampler, window, x->cap, nullptr);
     hipGraph_t g = nullptr;
     hipError_t e2 = hipStreamEndCapture(x->cap, &g);
     MX_TRY(x, e);
@@ -1127,7 +1181,7 @@ extern "C" int mx_llm_decode_profiled(mx_llm* x, int n_rows, void* stream,
   Prof prof;
   const int ml = decode_max_len(x, n_rows);
   hipError_t e = enqueue_decode(x, n_rows, ml, att_cpw_auto(x, n_rows, ml), sampler_of(x, n_rows),
-                                st, &prof);
+                                window_of(x, n_rows), st, &prof);
   mirror_step(x, n_rows);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   for (auto& p : prof.ev) {
@@ -1523,6 +1577,9 @@ extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
   } else if (k == "rows_atomic") {
     if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "rows_atomic must be 0 or 1");
     x->rows_atomic = value;
+  } else if (k == "grammar_head") {
+    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "grammar_head must be 0 or 1");
+    x->grammar_head = value;
   } else if (k == "head_b1") {
     if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "head_b1 must be 0 or 1");
     x->head_b1 = value;
@@ -1596,10 +1653,84 @@ extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
     MX_FAIL(x, MX_ERR_ARG, "unknown option " + k);
   }
   // captured graphs baked the old choice in: drop them
+  drop_graphs(x);
+  return MX_OK;
+}
+
+static void drop_graphs(mx_llm* x) {
   for (auto& kv : x->graphs) (void)hipGraphExecDestroy(kv.second);
   for (auto& kv : x->graph_defs) (void)hipGraphDestroy(kv.second);
   x->graphs.clear();
   x->graph_defs.clear();
+}
+
+extern "C" int mx_llm_set_grammar(mx_llm* x, const mx_code_grammar* g) {
+  if (!x) return MX_ERR_ARG;
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  for (char act : x->row_active)
+    if (act) MX_FAIL(x, MX_ERR_STATE, "set_grammar: a row is active");
+  const auto& c = x->c;
+  if (g) {
+    if (g->phases < 1 || g->codes < 1 || g->code_min < 0 || g->code_min >= g->codes || g->code_base < 0 ||
+        (long long)g->code_base + (long long)g->phases * g->codes > c.vocab)
+      MX_FAIL(x, MX_ERR_ARG, "grammar: need phases >= 1, codes >= 1, 0 <= code_min < codes, code_base >= 0, "
+                             "code_base + phases * codes <= vocab");
+    if (g->stop_id >= c.vocab ||
+        (g->stop_id >= g->code_base && g->stop_id < g->code_base + g->phases * g->codes))
+      MX_FAIL(x, MX_ERR_ARG, "grammar: stop_id inside a code range or past the vocabulary");
+  }
+  MX_TRY(x, hipSetDevice(x->device));
+  MX_TRY(x, hipDeviceSynchronize());
+  const size_t slots = (size_t)c.max_slots + 1;
+  // (allocated on the first call, behind every other buffer: a context that never sets a
+  // grammar keeps its allocations)
+  if (g && !x->gram_origin) MX_TRY(x, x->alloc(&x->gram_origin, slots));
+  if (x->gram_origin) MX_TRY(x, hipMemset(x->gram_origin, 0xFF, slots * 4));  // -1: unconstrained
+  std::fill(x->slot_grammar.begin(), x->slot_grammar.end(), 0);
+  std::fill(x->row_origin.begin(), x->row_origin.end(), -1);
+  x->gram_on = g != nullptr;
+  x->win_lo = x->win_n = 0;
+  x->win_heads = 0;
+  if (g) {
+    x->gram = *g;
+    // the row window: from the largest multiple of 256 not above the smallest allowed id to
+    // the end of the code ranges rounded up to 256 (capped by the vocabulary).  The kernels
+    // need a multiple of 4 rows (head_b1's row groups, the multi-row epilogue's 4-byte `seen`
+    // loads) and the multi-row workspace sized at create; a window that does not fit leaves
+    // every step on the whole vocabulary with the mask.
+    int first = g->code_base + g->code_min;
+    if (g->stop_id >= 0 && g->stop_id < first) first = g->stop_id;
+    int last = g->code_base + g->phases * g->codes;  // one past the last code
+    if (g->stop_id >= last) last = g->stop_id + 1;
+    const int lo = first / 256 * 256;
+    const int hi = (int)std::min<long long>(c.vocab, ((long long)last + 255) / 256 * 256);
+    bool fits = (hi - lo) % 4 == 0 && c.vocab % 4 == 0 && hi - lo < c.vocab;
+    for (int r : {16, 32, 64, c.max_batch}) {
+      size_t wf = 0, tk = 0;
+      v4::gemm_rows_workspace_v4(hi - lo, c.hidden, std::min(r, c.max_batch), EPI_ARGMAX, &wf, &tk);
+      if (wf > x->rows_ws_floats || tk > x->rows_tickets_n) fits = false;
+    }
+    if (fits) {
+      x->win_lo = lo;
+      x->win_n = hi - lo;
+    }
+  }
+  drop_graphs(x);
+  return MX_OK;
+}
+
+extern "C" int mx_llm_grammar_window(const mx_llm* x, int* lo, int* n, long long* heads) {
+  if (!x || !lo || !n || !heads) return MX_ERR_ARG;
+  *lo = x->win_lo;
+  *n = x->win_n;
+  *heads = x->win_heads;
+  return MX_OK;
+}
+
+extern "C" int mx_llm_set_slot_grammar(mx_llm* x, int slot, int on) {
+  if (!x || slot < 0 || slot >= x->c.max_slots) return MX_ERR_ARG;
+  if (on && !x->gram_on) MX_FAIL(x, MX_ERR_STATE, "set_slot_grammar: the context has no grammar");
+  x->slot_grammar[slot] = on ? 1 : 0;
   return MX_OK;
 }
 
@@ -1612,6 +1743,7 @@ extern "C" int mx_llm_release_row(mx_llm* x, int row, void* stream) {
   x->row_active[row] = 0;
   x->row_samples[row] = 0;
   x->row_chain[row] = 0;
+  x->row_origin[row] = -1;
   return MX_OK;
 }
 
@@ -1626,6 +1758,8 @@ extern "C" int mx_llm_move_row(mx_llm* x, int dst, int src, void* stream) {
   x->row_active[dst] = x->row_active[src];
   x->row_samples[dst] = x->row_samples[src];
   x->row_chain[dst] = x->row_chain[src];
+  x->row_origin[dst] = x->row_origin[src];
+  x->row_origin[src] = -1;
   x->pos_mirror[src] = 0;
   x->row_active[src] = 0;
   x->row_samples[src] = 0;
@@ -1654,6 +1788,17 @@ extern "C" int mx_llm_engine_trace(mx_llm* x, uint64_t* host_out, int n, int* gr
   return MX_OK;
 }
 
+// Allowed set of the token a stream of origin `origin` puts at position p: ids [lo, lo + n)
+// and `stop` (-1: none).
+static void allowed_span(const mx_llm* x, int origin, int p, int* lo, int* n, int* stop) {
+  const mx_code_grammar& g = x->gram;
+  int k = (p - origin) % g.phases;
+  if (k < 0) k += g.phases;
+  *lo = g.code_base + k * g.codes + g.code_min;
+  *n = g.codes - g.code_min;
+  *stop = k == 0 ? g.stop_id : -1;
+}
+
 extern "C" int mx_llm_debug_logits(mx_llm* x, int enable) {
   if (!x) return MX_ERR_ARG;
   if (!x->graphs.empty()) MX_FAIL(x, MX_ERR_STATE, "enable logits before the first decode");
@@ -1667,6 +1812,14 @@ extern "C" int mx_llm_read_logits(mx_llm* x, int row, float* host_out, void* str
   MX_TRY(x, hipMemcpyAsync(host_out, x->logits + (size_t)row * x->c.vocab,
                            (size_t)x->c.vocab * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   MX_TRY(x, hipStreamSynchronize((hipStream_t)stream));
+  // a constrained row: -inf outside the allowed set of the token the logits picked (the kernels
+  // skip those ids, and a windowed head does not compute most of them)
+  if (x->gram_on && x->row_origin[row] >= 0) {
+    int lo = 0, n = 0, stop = -1;
+    allowed_span(x, x->row_origin[row], x->pos_mirror[row], &lo, &n, &stop);
+    for (int i = 0; i < x->c.vocab; ++i)
+      if (!(i >= lo && i < lo + n) && i != stop) host_out[i] = -INFINITY;
+  }
   return MX_OK;
 }
 
@@ -1686,8 +1839,11 @@ extern "C" int mx_llm_debug_sample(mx_llm* x, int row, const float* logits_host,
   if (x->row_samples[row])
     MX_TRY(x, enqueue_sampler(x, lg, x->row_slot + row, x->dbg_pos + 1, 1, x->dbg_best,
                               x->row_chain[row] ? SMP_CHAIN : SMP_PLAIN, st));
-  else
-    MX_TRY(x, launch_argmax_row(lg, c.vocab, x->dbg_best, st));
+  else {
+    int lo = 0, n = c.vocab, stop = -1;
+    if (x->gram_on && x->row_origin[row] >= 0) allowed_span(x, x->row_origin[row], pos + 1, &lo, &n, &stop);
+    MX_TRY(x, launch_argmax_row(lg, lo, n, stop < 0 ? -1 : stop, x->dbg_best, st));
+  }
   unsigned long long key = 0ull;
   MX_TRY(x, hipMemcpyAsync(&key, x->dbg_best, 8, hipMemcpyDeviceToHost, st));
   MX_TRY(x, hipStreamSynchronize(st));

@@ -52,14 +52,15 @@ __device__ __forceinline__ EpiIn epi_load(const GemvArgs& a, int g, int ri, int 
   EpiIn e{};
   const int n = g * RPW + ri;
   if (F8) e.ws = a.wscale[n];
-  e.seen = a.seen[(size_t)slot * a.N + n];
+  e.seen = a.seen[(size_t)slot * a.V + a.id0 + n];
   return e;
 }
 
 template <int KCH, int RPW, bool F8>
 __device__ __forceinline__ void process(const GemvArgs& a, const float4* xs, int g, int lane,
                                         const uint4 (&w)[RPW][KCH], int ri, bool on, float pen,
-                                        bool keep, const EpiIn& e, unsigned long long& best) {
+                                        bool keep, const EpiIn& e, const GrammarSpan& sp,
+                                        unsigned long long& best) {
   constexpr int EPC = F8 ? 16 : 8;
   constexpr int PL = EPC / 4;
   constexpr int KC = KCH * 64;
@@ -120,11 +121,12 @@ __device__ __forceinline__ void process(const GemvArgs& a, const float4* xs, int
     }
   }
   if (!on) return;
-  const int n = g * RPW + ri;
+  const int id = a.id0 + g * RPW + ri;  // (the window's first row is id id0)
+  if (!grammar_allows(a.gram, sp, id)) return;  // outside the slot's allowed set: as -inf
   float y = F8 ? v[0] * e.ws : v[0];
   if (e.seen) y = y > 0.f ? y / pen : y * pen;
-  if (keep) a.logits[n] = y;
-  const unsigned long long key = argmax_key(y, (uint32_t)n);
+  if (keep) a.logits[id] = y;
+  const unsigned long long key = argmax_key(y, (uint32_t)id);
   best = key > best ? key : best;
 }
 
@@ -149,6 +151,9 @@ __global__ __launch_bounds__(NT, 1) void head_b1_kernel(GemvArgs a) {
   const int slot = a.row_slot[0];
   const float pen = a.penalty[slot];
   const bool keep = a.logits && (a.logits_all || a.samp_temp[slot] > 0.f);
+  // the slot's allowed ids (wave-uniform, loaded with the slot's other constants: nothing of
+  // the mask waits at the tail)
+  const GrammarSpan sp = grammar_span(a.gram, grammar_origin(a.gram, slot), a.gram.origin ? a.row_pos[0] : 0);
 
   // 1. the first group's weight loads, then the activation row under their latency
   uint4 w0[RPW][KCH], w1[RPW][KCH];
@@ -194,20 +199,20 @@ __global__ __launch_bounds__(NT, 1) void head_b1_kernel(GemvArgs a) {
       if (g + stride < G) {
         const EpiIn e = epi_load<RPW, F8>(a, g, ri, slot);
         load_group<KCH, RPW>(a, g + stride, lane, w1);
-        process<KCH, RPW, F8>(a, xs, g, lane, w0, ri, on, pen, keep, e, best);
+        process<KCH, RPW, F8>(a, xs, g, lane, w0, ri, on, pen, keep, e, sp, best);
       } else {
         const EpiIn e = epi_load<RPW, F8>(a, g, ri, slot);
-        process<KCH, RPW, F8>(a, xs, g, lane, w0, ri, on, pen, keep, e, best);
+        process<KCH, RPW, F8>(a, xs, g, lane, w0, ri, on, pen, keep, e, sp, best);
         break;
       }
       g += stride;
       if (g + stride < G) {
         const EpiIn e = epi_load<RPW, F8>(a, g, ri, slot);
         load_group<KCH, RPW>(a, g + stride, lane, w0);
-        process<KCH, RPW, F8>(a, xs, g, lane, w1, ri, on, pen, keep, e, best);
+        process<KCH, RPW, F8>(a, xs, g, lane, w1, ri, on, pen, keep, e, sp, best);
       } else {
         const EpiIn e = epi_load<RPW, F8>(a, g, ri, slot);
-        process<KCH, RPW, F8>(a, xs, g, lane, w1, ri, on, pen, keep, e, best);
+        process<KCH, RPW, F8>(a, xs, g, lane, w1, ri, on, pen, keep, e, sp, best);
         break;
       }
       g += stride;

@@ -153,17 +153,20 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
       for (int rt = 0; rt < RT; ++rt) {
         if (rt < nr) {
           const int slot = a.row_slot[r0 + rt];
-          const uint8_t* seen = a.seen + (size_t)slot * a.N;
+          const uint8_t* seen = a.seen + (size_t)slot * a.V;
           const float pen = a.penalty[slot];
           const bool keep = a.logits && (a.logits_all || a.samp_temp[slot] > 0.f);
+          // ids outside a constrained slot's allowed set count as -inf: no key, no logit
+          const GrammarSpan sp = grammar_span(a.gram, grammar_origin(a.gram, slot),
+                                              a.gram.origin ? a.row_pos[r0 + rt] : 0);
 #pragma unroll
           for (int i = 0; i < RPW; ++i) {
-            const int n = n0 + i;
-            if (n < a.N) {
+            const int n = n0 + i, id = a.id0 + n;  // (weight row n of the window is id id0 + n)
+            if (n < a.N && grammar_allows(a.gram, sp, id)) {
               float v = acc[i][rt];
-              if (seen[n]) v = v > 0.f ? v / pen : v * pen;
-              if (keep && lane == 0) a.logits[(size_t)(r0 + rt) * a.N + n] = v;
-              const unsigned long long key = argmax_key(v, (uint32_t)n);
+              if (seen[id]) v = v > 0.f ? v / pen : v * pen;
+              if (keep && lane == 0) a.logits[(size_t)(r0 + rt) * a.V + id] = v;
+              const unsigned long long key = argmax_key(v, (uint32_t)id);
               best[rt] = key > best[rt] ? key : best[rt];
             }
           }
@@ -1195,7 +1198,13 @@ static hipError_t launch_gemv1(const GemvArgs& a, int epi, bool norm, hipStream_
   return hipErrorNotSupported;
 }
 
-hipError_t launch_gemv(const GemvArgs& a, int epi, bool norm, hipStream_t st) {
+hipError_t launch_gemv(const GemvArgs& a_in, int epi, bool norm, hipStream_t st) {
+  GemvArgs a = a_in;
+  if (epi == EPI_ARGMAX) {
+    if (a.V == 0) a.V = a.N;  // the whole vocabulary: ids are the weight rows
+    // a grammar needs the rows' positions; a window must lie inside the vocabulary
+    if (a.id0 < 0 || a.id0 + a.N > a.V || (a.gram.origin && !a.row_pos)) return hipErrorInvalidValue;
+  }
   if (a.R == 1 && epi != EPI_ARGMAX && !a.force_legacy) {
     const hipError_t e = launch_gemv1(a, epi, norm, st);
     if (e != hipErrorNotSupported || a.att_ml) return e;  // (the merge has no other kernel)

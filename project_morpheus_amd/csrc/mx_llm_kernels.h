@@ -14,9 +14,48 @@ constexpr int ATT_MAXG = 4;         // max q-heads per kv-head
 constexpr int ATT_MERGE_CHUNK = 16; // splits whose partials the merging block prefetches
 constexpr int ATT_QKV_NKC_MAX = 8;  // qkv K ranges the attention sums (AttnArgs::qkv_parts)
 
+// Code grammar (DESIGN.md §3 "Code grammar"): the token a constrained slot puts at position p
+// has phase k = (p - origin[slot]) mod phases and may only be an id of
+//   A(k) = [base + k * codes + cmin, base + (k + 1) * codes)  plus {stop} when k == 0.
+// origin[slot] < 0 (or origin == null: no grammar on the context) leaves the slot unconstrained.
+struct GrammarArgs {
+  const int32_t* origin;   // per KV slot: the prefill's length, or -1; null = no grammar
+  int base, codes, phases, cmin, stop;
+};
+#ifdef __HIPCC__
+// A row's allowed set as (lo, stop): ids [lo, lo + codes - cmin) and `stop` (-1: none);
+// lo < 0 = unconstrained.  `pos` is the position of the row's input token: the token picked
+// takes pos + 1.
+struct GrammarSpan {
+  int lo, stop;
+};
+__device__ __forceinline__ GrammarSpan grammar_span(const GrammarArgs& g, int origin, int pos) {
+  GrammarSpan s{-1, -1};
+  if (origin >= 0) {
+    int k = (pos + 1 - origin) % g.phases;
+    k += k < 0 ? g.phases : 0;
+    s.lo = g.base + k * g.codes + g.cmin;
+    s.stop = k == 0 ? g.stop : -1;
+  }
+  return s;
+}
+// the span back from its first id alone (phase 0 is the only one that starts at base + cmin)
+__device__ __forceinline__ GrammarSpan grammar_span_of(const GrammarArgs& g, int lo) {
+  return GrammarSpan{lo, lo == g.base + g.cmin ? g.stop : -1};
+}
+__device__ __forceinline__ int grammar_origin(const GrammarArgs& g, int slot) {
+  return g.origin ? g.origin[slot] : -1;
+}
+__device__ __forceinline__ bool grammar_allows(const GrammarArgs& g, const GrammarSpan& s, int id) {
+  return s.lo < 0 || (unsigned)(id - s.lo) < (unsigned)(g.codes - g.cmin) || id == s.stop;
+}
+#endif
+
 struct GemvArgs {
   const void* W;           // [N][K] bf16 (WT_BF16) or e4m3 bytes (WT_FP8), packed row order
   const void* Wf;          // null, or the same matrix fragment-major (launch_frag_major) for R >= 2
+  int wf_t0, wf_T;         // Wf of a row window: its first 16-row tile and the tile count of the
+                           // whole matrix (the bf16 copy is sub-chunk-major over all tiles); 0, 0 = all
   const float* wscale;     // WT_FP8: dequant scale per row [N]
   int wdtype;
   int N, K;
@@ -66,12 +105,17 @@ struct GemvArgs {
   const float* att_acc;    // [kv_heads][att_stride][grp][128]
   int att_S, att_stride;   // split length (positions) and partial slots per kv head
   int att_nsm;             // splits the launch may have to merge (host bound, <= 8)
-  // EPI_ARGMAX
-  const uint8_t* seen;     // [slots][N]
+  // EPI_ARGMAX.  The launch may cover a row window of the lm_head: weight row n is id id0 + n,
+  // and `seen`, `logits` and the argmax key are indexed by id with the vocabulary V as stride
+  // (launch_gemv sets V = N when it is 0).  Rows of constrained slots skip ids outside their
+  // allowed set (`gram`; row_pos gives the phase).
+  int id0, V;
+  GrammarArgs gram;
+  const uint8_t* seen;     // [slots][V]
   const float* penalty;    // repetition penalty per KV slot [slots]
   const float* samp_temp;  // sampling temperature per KV slot (> 0: the row samples)
   unsigned long long* best;  // [R]
-  float* logits;           // penalised logits [R][N], kept for sampling rows (or every row)
+  float* logits;           // penalised logits [R][V], kept for sampling rows (or every row)
   int logits_all;          // 1: keep every row's logits (parity / debug reads)
 };
 
@@ -145,6 +189,7 @@ struct SampleArgs {
   const uint32_t* seed;    // per KV slot: Philox key (lo, hi)
   unsigned long long* best;  // [R] argmax-key encoded token (read by commit)
   int V;
+  GrammarArgs gram;        // constrained rows sweep their allowed span only
 };
 hipError_t launch_sample(const SampleArgs& a, int R, hipStream_t st);
 // the sampler with the top-k / min-p filters in front of the nucleus (sample_chain_kernel)
@@ -154,9 +199,11 @@ struct SampleChainArgs {
   const float* min_p;      // per KV slot: 0 = off
 };
 hipError_t launch_sample_chain(const SampleChainArgs& a, int R, hipStream_t st);
-// best[0] = argmax key of logits[0, V) (smallest index among equal maxima)
-hipError_t launch_argmax_row(const float* logits, int V, unsigned long long* best,
-                             hipStream_t st);
+// best[0] = argmax key of logits over the ids [lo, lo + n) and `stop` (-1: none): the smallest
+// index among equal maxima
+hipError_t launch_argmax_row(const float* logits, int lo, int n, int stop,
+                             unsigned long long* best, hipStream_t st);
+hipError_t launch_set_slot_origin(int32_t* origin, int slot, int value, hipStream_t st);
 hipError_t launch_set_slot_params(float* penalty, float* temp, float* top_p, uint32_t* seed,
                                   int slot, float pen, float t, float p, uint64_t s,
                                   hipStream_t st);

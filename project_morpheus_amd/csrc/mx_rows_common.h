@@ -32,7 +32,7 @@ __device__ __forceinline__ void split_parts(float* x, bf16x8* f) {
 // Operands of the epilogue that do not depend on the GEMM result, loaded BEFORE the split-K
 // hand-off (drain, ticket, merge loads) so that their round trips -- two dependent ones for
 // RoPE (row position, then the table) -- overlap it instead of following it.
-template <int MT, int NT, int EPI>
+template <int MT, int NT, int EPI, bool GRAM = false>
 struct EpiPre {
   float y[EPI == EPI_RESID ? MT : 1][EPI == EPI_RESID ? NT : 1][4];    // RESID: Y before the add
   float cs[EPI == EPI_QKV ? MT : 1][EPI == EPI_QKV ? NT : 1][2];       // QKV: RoPE per pair
@@ -45,6 +45,9 @@ struct EpiPre {
   float apen[EPI == EPI_ARGMAX ? NT : 1];
   int akeep[EPI == EPI_ARGMAX ? NT : 1];
   uint32_t aseen[EPI == EPI_ARGMAX ? MT : 1][EPI == EPI_ARGMAX ? NT : 1];
+  // ... and, in the grammar kernels (GRAM), the rows' positions, replaced by the first id of
+  // their allowed spans (GrammarSpan::lo; the stop id follows from it: grammar_span_of)
+  int alo[EPI == EPI_ARGMAX && GRAM ? NT : 1];
 };
 
 // The lm_head epilogue's operands hang off the row's slot (row_slot -> seen / penalty): two
@@ -52,26 +55,33 @@ struct EpiPre {
 // block at 8 rows, profiles/r05_rows_block_trace.log).  The slot loads go out at the top of
 // sub-chunk SUB - 2, the dependent loads at the top of SUB - 1 (behind every weight load, so
 // vmcnt stays exact), both under the last sub-chunks' weight latency.
-template <int MT, int NT, int EPI>
-__device__ __forceinline__ void argmax_slots(const GemvArgs& a, EpiPre<MT, NT, EPI>& P, int r0, int c) {
+template <int MT, int NT, int EPI, bool GRAM>
+__device__ __forceinline__ void argmax_slots(const GemvArgs& a, EpiPre<MT, NT, EPI, GRAM>& P, int r0, int c) {
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-    P.aslot[nt % (EPI == EPI_ARGMAX ? NT : 1)] = a.row_slot[min(r0 + 16 * nt + c, a.R - 1)];
+  for (int nt = 0; nt < NT; ++nt) {
+    const int b = min(r0 + 16 * nt + c, a.R - 1);
+    P.aslot[nt % (EPI == EPI_ARGMAX ? NT : 1)] = a.row_slot[b];
+    if constexpr (GRAM) P.alo[nt % (EPI == EPI_ARGMAX ? NT : 1)] = a.row_pos[b];
+  }
 }
-template <int MT, int NT, int EPI>
-__device__ __forceinline__ void argmax_operands(const GemvArgs& a, EpiPre<MT, NT, EPI>& P, int n0, int g) {
+template <int MT, int NT, int EPI, bool GRAM>
+__device__ __forceinline__ void argmax_operands(const GemvArgs& a, EpiPre<MT, NT, EPI, GRAM>& P, int n0, int g) {
   constexpr int ANT = EPI == EPI_ARGMAX ? NT : 1, AMT = EPI == EPI_ARGMAX ? MT : 1;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int slot = P.aslot[nt % ANT];
     P.apen[nt % ANT] = a.penalty[slot];
     P.akeep[nt % ANT] = a.logits && (a.logits_all || a.samp_temp[slot] > 0.f);
-    const uint8_t* seen = a.seen + (size_t)slot * a.N;
+    if constexpr (GRAM) P.alo[nt % ANT] = grammar_span(a.gram, a.gram.origin[slot], P.alo[nt % ANT]).lo;
+    // (weight row n of a row window is id id0 + n; id0 is a multiple of 4.  Only the grammar
+    // kernels run a window: the others have id0 = 0 and V = N)
+    const int V = GRAM ? a.V : a.N;
+    const uint8_t* seen = a.seen + (size_t)slot * V + (GRAM ? a.id0 : 0);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const int nb = n0 + 16 * mt + 4 * g;
       uint32_t v = 0;
-      if ((a.N & 3) == 0) {
+      if (((a.N | V) & 3) == 0) {
         v = *reinterpret_cast<const uint32_t*>(seen + min(nb, a.N - 4));
       } else {
 #pragma unroll
@@ -83,8 +93,8 @@ __device__ __forceinline__ void argmax_operands(const GemvArgs& a, EpiPre<MT, NT
   }
 }
 
-template <int MT, int NT, int EPI>
-__device__ __forceinline__ void rows_epilogue_pre(const GemvArgs& a, EpiPre<MT, NT, EPI>& P,
+template <int MT, int NT, int EPI, bool GRAM>
+__device__ __forceinline__ void rows_epilogue_pre(const GemvArgs& a, EpiPre<MT, NT, EPI, GRAM>& P,
                                                   int n0, int r0, int c, int g) {
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
@@ -128,10 +138,10 @@ __device__ __forceinline__ void rows_epilogue_pre(const GemvArgs& a, EpiPre<MT, 
 
 // Epilogue of one wave's tile: lane (batch col c, group g) holds weight rows
 // n0 + 16 mt + 4 g + i for batch rows r0 + 16 nt + c (MFMA C/D layout).
-template <int MT, int NT, int EPI>
+template <int MT, int NT, int EPI, bool GRAM>
 __device__ __forceinline__ void rows_epilogue(const GemvArgs& a, f32x4 (&acc)[MT][NT],
                                               const float (&scale)[NT], int n0, int r0, int c,
-                                              int g, const EpiPre<MT, NT, EPI>& P) {
+                                              int g, const EpiPre<MT, NT, EPI, GRAM>& P) {
   unsigned long long best[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) best[nt] = 0ull;
@@ -199,14 +209,17 @@ __device__ __forceinline__ void rows_epilogue(const GemvArgs& a, f32x4 (&acc)[MT
         const float pen = P.apen[nt % ANT];
         const bool keep = P.akeep[nt % ANT];
         const uint32_t sn = P.aseen[mt % AMT][nt % ANT];
+        const int id0 = GRAM ? a.id0 : 0, V = GRAM ? a.V : a.N;
+        const GrammarSpan sp = GRAM ? grammar_span_of(a.gram, P.alo[nt % ANT]) : GrammarSpan{-1, -1};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const int n = nb + i;
-          if (n >= a.N) continue;
+          const int n = nb + i, id = id0 + n;
+          // (ids outside a constrained slot's allowed set count as -inf: no key, no logit)
+          if (n >= a.N || (GRAM && !grammar_allows(a.gram, sp, id))) continue;
           float x = v[i];
           if ((sn >> (8 * i)) & 0xffu) x = x > 0.f ? x / pen : x * pen;
-          if (keep) a.logits[(size_t)b * a.N + n] = x;
-          const unsigned long long key = argmax_key(x, (uint32_t)n);
+          if (keep) a.logits[(size_t)b * V + id] = x;
+          const unsigned long long key = argmax_key(x, (uint32_t)id);
           best[nt] = key > best[nt] ? key : best[nt];
         }
       }

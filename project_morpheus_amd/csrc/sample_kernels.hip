@@ -17,6 +17,10 @@
 //           (23 bits: u + 0.5 is exact in fp32, so u is strictly inside (0, 1))
 //   token = argmax_{kept i} e_i / q_i  (smallest index on ties)   -- the exponential race,
 //           an exact draw from the renormalised kept distribution.
+// A slot under the context's code grammar (Code grammar) has l_i = -inf outside
+// its allowed set A(k): e_i = 0 there, so such ids carry no mass and are never kept.  The
+// kernels below therefore sweep A(k) alone -- one span of ids plus at most one stop id -- and
+// compute the same sums, counts and race as a sweep over the masked vocabulary.
 // Integer masses make the nucleus cut order-independent (deterministic under atomics); the
 // cut is found by a 3-pass radix select over the bit pattern of e_i (12 + 12 + 8 bits) with
 // per-bin masses in LDS, one 1024-thread block per row.
@@ -102,7 +106,14 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
   const uint32_t ctr1 = (uint32_t)a.row_pos[r];
   const float* lg = a.logits + (size_t)r * a.V;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int V = a.V;
+  // the ids the row may pick: every id, or a constrained slot's span [lo, lo + span_n) plus its
+  // stop id.  Sweep element j is id id_of(j); everything below is a sum, a histogram or a
+  // maximum over the swept ids, and the Philox counter is the id, so the order does not matter.
+  const GrammarSpan sp = grammar_span(a.gram, grammar_origin(a.gram, slot), a.row_pos[r]);
+  const int span_lo = sp.lo < 0 ? 0 : sp.lo;
+  const int span_n = sp.lo < 0 ? a.V : a.gram.codes - a.gram.cmin;
+  const int n_it = span_n + (sp.stop >= 0 ? 1 : 0);
+  auto id_of = [&](int j) { return j < span_n ? span_lo + j : sp.stop; };
 
   __shared__ unsigned long long hist[4096];
   __shared__ unsigned long long wsum[SMP_T / 64];
@@ -112,7 +123,7 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
 
   // pass 1: max logit
   float m = -INFINITY;
-  for (int i = t; i < V; i += SMP_T) m = fmaxf(m, lg[i]);
+  for (int j = t; j < n_it; j += SMP_T) m = fmaxf(m, lg[id_of(j)]);
   m = wave_max(m);
   if (lane == 0) fred[w] = m;
   for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
@@ -124,7 +135,8 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
 
   // pass 2: total integer mass Z and the first radix histogram (bits 31..20 of e)
   unsigned long long z = 0ull;
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     const unsigned long long f = f_of(e);
     z += f;
@@ -148,7 +160,8 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
   // pass 3: bits 19..8 inside bin b1
   for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
   __syncthreads();
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     const uint32_t bits = __float_as_uint(e);
     if ((bits >> 20) == b1) {
@@ -164,7 +177,8 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
   // pass 4: bits 7..0 inside (b1, b2)
   for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
   __syncthreads();
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     const uint32_t bits = __float_as_uint(e);
     if ((bits >> 8) == b12) {
@@ -178,7 +192,8 @@ __global__ __launch_bounds__(SMP_T) void sample_kernel(SampleArgs a) {
 
   // pass 5: exponential race over the kept tokens
   unsigned long long best = 0ull;
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     if (__float_as_uint(e) >= tcut) {
       const uint32_t x = philox_x0((uint32_t)i, ctr1, k0, k1);
@@ -224,7 +239,14 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
   const uint32_t ctr1 = (uint32_t)a.row_pos[r];
   const float* lg = a.logits + (size_t)r * a.V;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int V = a.V;
+  // the ids the row may pick: every id, or a constrained slot's span [lo, lo + span_n) plus its
+  // stop id.  Sweep element j is id id_of(j); everything below is a sum, a histogram or a
+  // maximum over the swept ids, and the Philox counter is the id, so the order does not matter.
+  const GrammarSpan sp = grammar_span(a.gram, grammar_origin(a.gram, slot), a.row_pos[r]);
+  const int span_lo = sp.lo < 0 ? 0 : sp.lo;
+  const int span_n = sp.lo < 0 ? a.V : a.gram.codes - a.gram.cmin;
+  const int n_it = span_n + (sp.stop >= 0 ? 1 : 0);
+  auto id_of = [&](int j) { return j < span_n ? span_lo + j : sp.stop; };
 
   __shared__ unsigned long long hist[4096];
   __shared__ unsigned long long wsum[SMP_T / 64];
@@ -234,7 +256,7 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
 
   // pass 1: max logit
   float m = -INFINITY;
-  for (int i = t; i < V; i += SMP_T) m = fmaxf(m, lg[i]);
+  for (int j = t; j < n_it; j += SMP_T) m = fmaxf(m, lg[id_of(j)]);
   m = wave_max(m);
   if (lane == 0) fred[w] = m;
   for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
@@ -246,11 +268,12 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
 
   // the filter threshold: min_p's bits (positive floats order as their bit patterns) ...
   uint32_t fbits = min_p > 0.f ? __float_as_uint(min_p) : 0u;
-  // ... and, for 0 < top_k < V, the k-th largest e among the tokens with f > 0
-  if (top_k > 0 && top_k < V) {
+  // ... and, for 0 < top_k < the ids swept, the k-th largest e among the tokens with f > 0
+  if (top_k > 0 && top_k < n_it) {
     // count pass 1: how many tokens have f > 0, and their histogram over bits 31..20 of e
     unsigned long long n = 0ull;
-    for (int i = t; i < V; i += SMP_T) {
+    for (int j = t; j < n_it; j += SMP_T) {
+      const int i = id_of(j);
       const float e = e_of(i);
       if (f_of(e)) {
         ++n;
@@ -272,7 +295,8 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
     // count pass 2: bits 19..8 inside bin kb1
     for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
     __syncthreads();
-    for (int i = t; i < V; i += SMP_T) {
+    for (int j = t; j < n_it; j += SMP_T) {
+      const int i = id_of(j);
       const float e = e_of(i);
       const uint32_t bits = __float_as_uint(e);
       if ((bits >> 20) == kb1 && f_of(e)) atomicAdd(&hist[(bits >> 8) & 0xFFFu], 1ull);
@@ -285,7 +309,8 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
     // count pass 3: bits 7..0 inside (kb1, kb2)
     for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
     __syncthreads();
-    for (int i = t; i < V; i += SMP_T) {
+    for (int j = t; j < n_it; j += SMP_T) {
+      const int i = id_of(j);
       const float e = e_of(i);
       const uint32_t bits = __float_as_uint(e);
       if ((bits >> 8) == kb12 && f_of(e)) atomicAdd(&hist[bits & 0xFFu], 1ull);
@@ -301,7 +326,8 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
 
   // mass pass 1: Z over F and the first radix histogram (bits 31..20 of e)
   unsigned long long z = 0ull;
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     const uint32_t bits = __float_as_uint(e);
     const unsigned long long f = bits >= fbits ? f_of(e) : 0ull;
@@ -326,7 +352,8 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
   // mass pass 2: bits 19..8 inside bin b1
   for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
   __syncthreads();
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     const uint32_t bits = __float_as_uint(e);
     if ((bits >> 20) == b1 && bits >= fbits) {
@@ -342,7 +369,8 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
   // mass pass 3: bits 7..0 inside (b1, b2)
   for (int i = t; i < 4096; i += SMP_T) hist[i] = 0ull;
   __syncthreads();
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     const uint32_t bits = __float_as_uint(e);
     if ((bits >> 8) == b12 && bits >= fbits) {
@@ -357,7 +385,8 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
 
   // race pass: exponential race over the kept tokens
   unsigned long long best = 0ull;
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n_it; j += SMP_T) {
+    const int i = id_of(j);
     const float e = e_of(i);
     if (__float_as_uint(e) >= tcut) {
       const uint32_t x = philox_x0((uint32_t)i, ctr1, k0, k1);
@@ -382,12 +411,13 @@ __global__ __launch_bounds__(SMP_T) void sample_chain_kernel(SampleChainArgs c) 
 }
 
 // Argmax key of one row of caller logits (the greedy branch of mx_llm_debug_sample).
-__global__ __launch_bounds__(SMP_T) void argmax_row_kernel(const float* lg, int V,
+__global__ __launch_bounds__(SMP_T) void argmax_row_kernel(const float* lg, int lo, int n, int stop,
                                                           unsigned long long* out) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   __shared__ unsigned long long wbest[SMP_T / 64];
   unsigned long long best = 0ull;
-  for (int i = t; i < V; i += SMP_T) {
+  for (int j = t; j < n + (stop >= 0 ? 1 : 0); j += SMP_T) {
+    const int i = j < n ? lo + j : stop;
     const unsigned long long key = argmax_key(lg[i], (uint32_t)i);
     best = key > best ? key : best;
   }
@@ -412,6 +442,8 @@ __global__ void set_slot_ext_kernel(int32_t* top_k, float* min_p, int32_t* last_
   last_n[slot] = n;
 }
 
+__global__ void set_slot_origin_kernel(int32_t* origin, int slot, int value) { origin[slot] = value; }
+
 __global__ void set_slot_params_kernel(float* penalty, float* temp, float* top_p,
                                        uint32_t* seed, int slot, float pen, float t, float p,
                                        uint32_t s0, uint32_t s1) {
@@ -432,9 +464,14 @@ hipError_t launch_sample_chain(const SampleChainArgs& a, int R, hipStream_t st) 
   return hipGetLastError();
 }
 
-hipError_t launch_argmax_row(const float* logits, int V, unsigned long long* best,
-                             hipStream_t st) {
-  hipLaunchKernelGGL(argmax_row_kernel, dim3(1), dim3(SMP_T), 0, st, logits, V, best);
+hipError_t launch_argmax_row(const float* logits, int lo, int n, int stop,
+                             unsigned long long* best, hipStream_t st) {
+  hipLaunchKernelGGL(argmax_row_kernel, dim3(1), dim3(SMP_T), 0, st, logits, lo, n, stop, best);
+  return hipGetLastError();
+}
+
+hipError_t launch_set_slot_origin(int32_t* origin, int slot, int value, hipStream_t st) {
+  hipLaunchKernelGGL(set_slot_origin_kernel, dim3(1), dim3(1), 0, st, origin, slot, value);
   return hipGetLastError();
 }
 

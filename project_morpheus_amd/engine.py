@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import ENGINE_OPTIONS, STOP_IDS, OrpheusConfig, rope_tables
+from .config import (ENGINE_OPTIONS, ORPHEUS_GRAMMAR, STOP_IDS, OrpheusConfig, grammar_default,
+                     rope_tables)
 from .schedule import WindowScheduler, code_of_id, frames_for_slice
 
 SAMPLES_PER_FRAME = 2048
@@ -72,6 +73,8 @@ class LlmEngine:
         cos, sin = rope_tables(cfg, max_pos)
         self._check(self.lib.mx_llm_set_rope(h, cos.ctypes.data, sin.ctypes.data, max_pos))
         self._check(self.lib.mx_llm_finalize(h))
+        self.grammar = None          # config.CodeGrammar of the context (set_grammar)
+        self._slot_grammar = {}      # slot -> constrained flag as last sent to the library
         for key, val in ENGINE_OPTIONS.items():   # MORPHEUS_MX_OPT_<key>=<int> overrides
             self.set_option(key, val)
         hp = self.lib.mx_llm_history(h)
@@ -84,11 +87,17 @@ class LlmEngine:
 
     def prefill(self, slot: int, row: int, ids: Sequence[int], penalty: float, stream, *,
                 temperature: float = 0.0, top_p: float = 1.0, seed: int = 0,
-                top_k: int = 0, min_p: float = 0.0, penalty_last_n: int = 0) -> None:
+                top_k: int = 0, min_p: float = 0.0, penalty_last_n: int = 0,
+                grammar: bool = False) -> None:
         """Prefill ``ids`` into KV ``slot`` bound to decode ``row``; the slot decodes under
         (penalty, temperature, top_p, seed) until the next prefill (temperature 0 = greedy).
         ``top_k`` / ``min_p`` filter before the nucleus (0 = off); ``penalty_last_n`` = N > 0
-        penalises the ids of the last N positions only (0 = the whole sequence, N <= 255)."""
+        penalises the ids of the last N positions only (0 = the whole sequence, N <= 255).
+        ``grammar``: the stream picks from the allowed ids of the engine's code grammar only
+        (``set_grammar`` first)."""
+        if bool(grammar) != self._slot_grammar.get(slot, False):
+            self._check(self.lib.mx_llm_set_slot_grammar(self.h, slot, int(bool(grammar))))
+            self._slot_grammar[slot] = bool(grammar)
         arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
         sp = _lib.Sampling(temperature=float(temperature), top_p=float(top_p),
                            repetition_penalty=float(penalty), seed=int(seed) & (2**64 - 1))
@@ -168,6 +177,16 @@ class LlmEngine:
     def set_option(self, key: str, value: int) -> None:
         self._check(self.lib.mx_llm_set_option(self.h, key.encode(), int(value)))
 
+    def set_grammar(self, grammar=ORPHEUS_GRAMMAR) -> None:
+        """Give the context a code grammar (``config.CodeGrammar``; ``None`` clears it).  Idle
+        engine only.  Streams prefilled with ``grammar=True`` then pick from its allowed ids."""
+        g = None if grammar is None else _lib.CodeGrammar(
+            code_base=grammar.code_base, codes=grammar.codes, phases=grammar.phases,
+            code_min=grammar.code_min, stop_id=grammar.stop_id)
+        self._check(self.lib.mx_llm_set_grammar(self.h, None if g is None else C.byref(g)))
+        self.grammar = grammar
+        self._slot_grammar = {}
+
     def enable_logits(self) -> None:
         """Parity/debug mode: keep the penalised logits of each row (before first decode)."""
         self._check(self.lib.mx_llm_debug_logits(self.h, 1))
@@ -190,6 +209,14 @@ class LlmEngine:
         self._check(self.lib.mx_llm_debug_sample(self.h, row, lg.ctypes.data, int(pos),
                                                  C.byref(tok), C.c_void_p(stream.cuda_stream)))
         return tok.value
+
+    def grammar_window(self):
+        """(lo, n, heads): the grammar's lm_head row window [lo, lo + n) (n 0: none) and the
+        number of lm_head launches issued over it since ``set_grammar`` (a launch captured
+        into a step graph counts once)."""
+        lo, n, heads = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        self._check(self.lib.mx_llm_grammar_window(self.h, C.byref(lo), C.byref(n), C.byref(heads)))
+        return lo.value, n.value, heads.value
 
     def row_state(self, row: int):
         """(active, next position) of decode row ``row`` (host view)."""
@@ -334,9 +361,11 @@ class Synthesizer:
             stats: Optional[UtteranceStats] = None, slot: int = 0, row: int = 0,
             temperature: float = 0.0, top_p: float = 1.0, seed: int = 0,
             noise_seed: Optional[int] = None, top_k: int = 0, min_p: float = 0.0,
-            penalty_last_n: int = 0) -> Iterator[bytes]:
+            penalty_last_n: int = 0, grammar: Optional[bool] = None) -> Iterator[bytes]:
         """Prefill, then decode up to ``max_tokens`` tokens (engine_class.py:103-134), greedy
         unless ``temperature`` > 0.  Window j's SNAC noise is drawn from (noise_seed, j).
+        ``grammar``: decode under the Orpheus code grammar (set on the engine if it has none);
+        None = ``config.grammar_default()`` (MORPHEUS_MX_GRAMMAR).
 
         ``inject_ids`` (bench / synthetic weights): token ids fed to the SNAC
         schedule in place of the model's own tokens; the LLM still decodes every step.
@@ -350,9 +379,12 @@ class Synthesizer:
         inflight: deque = deque()  # (token index, event)
         stop = set(int(s) for s in stop_ids)
 
+        grammar = grammar_default() if grammar is None else bool(grammar)
+        if grammar and llm.grammar is None:
+            llm.set_grammar(ORPHEUS_GRAMMAR)
         llm.prefill(slot, row, prompt_ids, penalty, self.stream, temperature=temperature,
                     top_p=top_p, seed=seed, top_k=top_k, min_p=min_p,
-                    penalty_last_n=penalty_last_n)
+                    penalty_last_n=penalty_last_n, grammar=grammar)
         ev = torch.cuda.Event()
         ev.record(self.stream)
         inflight.append((0, ev))

@@ -85,8 +85,10 @@ class Service:
                penalty: float = I.REPETITION_PENALTY, temperature: Optional[float] = None,
                top_p: Optional[float] = None, seed: Optional[int] = None,
                prompt_ids=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-               penalty_last_n: Optional[int] = None) -> StreamHandle:
-        """Queue one utterance on this GPU's batch loop (non-blocking)."""
+               penalty_last_n: Optional[int] = None,
+               grammar: Optional[bool] = None) -> StreamHandle:
+        """Queue one utterance on this GPU's batch loop (non-blocking).  ``grammar``: decode
+        under the Orpheus code grammar (None: MORPHEUS_MX_GRAMMAR, off when unset)."""
         ids = list(prompt_ids) if prompt_ids is not None else self.prompt_ids(text, voice)
         max_tokens = max_tokens or I.MAX_TOKENS
         # one utterance's random streams (sampling, SNAC noise, synthetic codes) come from ONE
@@ -100,6 +102,7 @@ class Service:
             top_k=I.TOP_K if top_k is None else top_k,
             min_p=I.MIN_P if min_p is None else min_p,
             penalty_last_n=I.REPEAT_LAST_N if penalty_last_n is None else penalty_last_n,
+            grammar=C.grammar_default() if grammar is None else bool(grammar),
             inject_ids=C.synthetic_audio_ids(max_tokens, seed=key)
             if self.synthetic_audio else None)
         if self.synthetic_audio:
@@ -110,7 +113,7 @@ class Service:
                       temperature: Optional[float] = None, top_p: Optional[float] = None,
                       penalty: float = I.REPETITION_PENALTY, seed: Optional[int] = None,
                       top_k: Optional[int] = None, min_p: Optional[float] = None,
-                      penalty_last_n: Optional[int] = None):
+                      penalty_last_n: Optional[int] = None, grammar: Optional[bool] = None):
         """Token-only stream (completions surface): a TokenHandle of generated ids."""
         ids = list(prompt_ids)
         key = C.request_seed(ids, seed)
@@ -121,7 +124,8 @@ class Service:
                             top_k=I.TOP_K if top_k is None else top_k,
                             min_p=I.MIN_P if min_p is None else min_p,
                             penalty_last_n=I.REPEAT_LAST_N if penalty_last_n is None
-                            else penalty_last_n)
+                            else penalty_last_n,
+                            grammar=C.grammar_default() if grammar is None else bool(grammar))
         return self.batch.submit(req)
 
     def stream(self, text: str, voice: str = I.DEFAULT_VOICE, max_tokens: Optional[int] = None,
