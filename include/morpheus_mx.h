@@ -120,6 +120,34 @@ int mx_llm_prefill(mx_llm* ctx, int slot, int row, const int32_t* ids_host, int 
  * state, so whole-sequence and windowed requests may follow each other on one slot. */
 int mx_llm_prefill_ex(mx_llm* ctx, int slot, int row, const int32_t* ids_host, int n_ids,
                       const mx_sampling* params, const mx_sampling_ext* ext, void* stream);
+/* Packed prefill: admit n_segs streams in ONE pass over the weights.  The prompts' rows run
+ * the layers as one row set (R = sum of n_ids), one lm_head launch covers the n_segs last rows,
+ * one sampler node picks every first token.  Afterwards the context is in the state n_segs
+ * calls of mx_llm_prefill_ex in segment order would leave, up to fp32 summation order: KV,
+ * penalty state, slot parameters and extras, grammar origins (per mx_llm_set_slot_grammar), row
+ * bindings, first tokens, history, next inputs, and mx_llm_read_logits(row).  Every check runs
+ * before anything is enqueued, so a refused call leaves the context as it was: MX_ERR_ARG on
+ * n_segs outside [1, max_batch], sum n_ids > max_prefill, an n_ids < 1 or >= max_pos, a slot or
+ * row out of range or named twice, an id out of vocab, or sampling values mx_llm_prefill_ex
+ * refuses; MX_ERR_STATE before finalize.
+ * Layout (64-bit ABI; checked by the static_assert below and by the ctypes binding):
+ *   offset 0 slot, 4 row, 8 ids_host, 16 n_ids, 24 params (24 bytes), 48 ext (12 bytes);
+ *   sizeof 64. */
+typedef struct mx_prefill_seg {
+  int32_t slot, row;          /* KV slot, decode row the stream is bound to */
+  const int32_t* ids_host;    /* prompt ids (host) */
+  int32_t n_ids;
+  mx_sampling params;
+  mx_sampling_ext ext;        /* all zero = neutral */
+} mx_prefill_seg;
+#ifdef __cplusplus
+static_assert(sizeof(void*) != 8 ||
+                  (sizeof(mx_prefill_seg) == 64 && offsetof(mx_prefill_seg, row) == 4 &&
+                   offsetof(mx_prefill_seg, ids_host) == 8 && offsetof(mx_prefill_seg, n_ids) == 16 &&
+                   offsetof(mx_prefill_seg, params) == 24 && offsetof(mx_prefill_seg, ext) == 48),
+              "mx_prefill_seg layout");
+#endif
+int mx_llm_prefill_batch(mx_llm* ctx, const mx_prefill_seg* segs, int n_segs, void* stream);
 /* One decode step for rows [0, n_rows), each under its slot's parameters (hipGraph-captured
  * per row count and attention grid; replayed). */
 int mx_llm_decode(mx_llm* ctx, int n_rows, void* stream);

@@ -56,6 +56,12 @@ class SamplingExt(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("min_p", C.c_float), ("penalty_last_n", C.c_int32)]
 
 
+class PrefillSeg(C.Structure):
+    """mx_prefill_seg: one stream of a packed prefill (mx_llm_prefill_batch)."""
+    _fields_ = [("slot", C.c_int32), ("row", C.c_int32), ("ids_host", C.c_void_p),
+                ("n_ids", C.c_int32), ("params", Sampling), ("ext", SamplingExt)]
+
+
 class CodeGrammar(C.Structure):
     """mx_code_grammar: ids [code_base + k*codes + code_min, code_base + (k+1)*codes) at phase k,
     plus stop_id at phase 0."""
@@ -74,6 +80,7 @@ _SIGS = {
     "mx_llm_prefill": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(Sampling), _P]),
     "mx_llm_prefill_ex": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(Sampling),
                                     C.POINTER(SamplingExt), _P]),
+    "mx_llm_prefill_batch": (C.c_int, [_P, C.POINTER(PrefillSeg), C.c_int, _P]),
     "mx_llm_decode": (C.c_int, [_P, C.c_int, _P]),
     "mx_llm_check": (C.c_int, [_P, _P]),
     "mx_llm_decode_profiled": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_double), C.c_int]),

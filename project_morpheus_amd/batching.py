@@ -46,8 +46,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import BATCH_DEPTH, ORPHEUS_GRAMMAR, SNAC_MAX_HOLD, SNAC_MIN_BATCH, STOP_IDS
-from .engine import SAMPLES_PER_FRAME, SLICE_HI, SLICE_LO, LlmEngine, SnacDecoder
+from .config import (BATCH_DEPTH, ORPHEUS_GRAMMAR, SNAC_MAX_HOLD, SNAC_MIN_BATCH, STOP_IDS,
+                     packed_prefill_default)
+from .engine import (SAMPLES_PER_FRAME, SLICE_HI, SLICE_LO, LlmEngine, PrefillSegment,
+                     SnacDecoder)
 from .schedule import WindowScheduler, code_of_id, frames_for_slice
 
 _MASK48 = 0xFFFFFFFFFFFF
@@ -174,6 +176,25 @@ def plan_compaction(rows: List[_Row]) -> List[Tuple[int, int]]:
         hi.idx, lo.idx = i, j
 
 
+def plan_prefill_packs(lengths: Sequence[int], max_prefill: int, max_k: int) -> List[List[int]]:
+    """Packs of a burst of prompts for ``LlmEngine.prefill_batch``: indices into ``lengths`` in
+    arrival order, never reordered.  A pack is filled greedily and closed by the first prompt
+    that would take it past ``max_prefill`` rows or ``max_k`` streams.  (A prompt longer than
+    ``max_prefill`` lands in a pack of its own: refusing it is the caller's business.)"""
+    packs: List[List[int]] = []
+    cur: List[int] = []
+    rows = 0
+    for i, n in enumerate(lengths):
+        if cur and (rows + n > max_prefill or len(cur) >= max_k):
+            packs.append(cur)
+            cur, rows = [], 0
+        cur.append(i)
+        rows += n
+    if cur:
+        packs.append(cur)
+    return packs
+
+
 class _BatchRing:
     """Host-mapped staging for batched SNAC calls: codes and noise seeds in, PCM16 out."""
 
@@ -242,12 +263,17 @@ class TokenHandle(StreamHandle):
 class BatchSynthesizer:
     def __init__(self, llm: LlmEngine, snac: SnacDecoder, depth: Optional[int] = None, seed: int = 0,
                  snac_min_batch: Optional[int] = None, snac_max_hold: Optional[int] = None,
-                 compact: bool = True):
+                 compact: bool = True, packed_prefill: Optional[bool] = None):
         if llm.max_slots < llm.max_batch:
             raise ValueError("BatchSynthesizer needs one KV slot per decode row")
         self.llm, self.snac, self.seed = llm, snac, seed
         self.compact = compact  # row compaction (mx_llm_move_row) when streams end
         self.row_steps = collections.Counter()  # decode steps issued per row count (stats)
+        # packed prefill: the requests one iteration admits go through LlmEngine.prefill_batch,
+        # one pass over the weights per pack (None: MORPHEUS_MX_PACKED_PREFILL, off when unset)
+        self.packed_prefill = packed_prefill_default() if packed_prefill is None \
+            else bool(packed_prefill)
+        self.prefill_packs = collections.Counter()  # prefill_batch calls per stream count
         self.depth = max(1, BATCH_DEPTH if depth is None else depth)
         # SNAC window coalescing: due windows are held until `snac_min_batch` of them are
         # ready or the oldest has waited `snac_max_hold` decode steps (a stream's first window
@@ -392,10 +418,75 @@ class BatchSynthesizer:
                 llm.release_row(r.idx, self.stream)
                 r.parked = True
 
+        def bind(r: _Row, req: StreamRequest, slot: int, n0: int) -> None:
+            free_slots.discard(slot)
+            r.slot = slot
+            r.req, r.sched, r.n0 = req, WindowScheduler(), n0
+            r.limit = max(1, min(req.max_tokens, llm.max_pos - n0))
+            r.issued, r.stopped, r.parked = 1, False, False
+            req.t_admit = now()
+            live.append(req)
+
+        def prefill_one(r: _Row, req: StreamRequest, slot: int, n0: int) -> bool:
+            try:  # a request the device rejects fails alone; the loop serves on
+                check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
+                             top_k=req.top_k, min_p=req.min_p,
+                             penalty_last_n=req.penalty_last_n)
+                llm.prefill(slot, r.idx, req.prompt_ids, req.penalty, self.stream,
+                            temperature=req.temperature, top_p=req.top_p, seed=req.seed,
+                            top_k=req.top_k, min_p=req.min_p,
+                            penalty_last_n=req.penalty_last_n, grammar=bool(req.grammar))
+            except (ValueError, _lib.MxError) as e:
+                if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
+                    raise  # a device failure is not this request's fault
+                req.error = e
+                complete(req)
+                return False
+            bind(r, req, slot, n0)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+            inflight.append((ev, [(r, req, 0)]))
+            if r.issued >= r.limit:
+                park(r)
+            return True
+
+        def admit_packs(cands: List) -> None:
+            """cands: [(row, request, slot, prompt length)] in admission order, slots already
+            taken out of ``free_slots``: one ``prefill_batch`` per pack of the plan."""
+            plan = plan_prefill_packs([n0 for _, _, _, n0 in cands], llm.max_prefill, B)
+            for pack in plan:
+                items = [cands[i] for i in pack]
+                segs = [PrefillSegment(
+                    slot=slot, row=r.idx, ids=req.prompt_ids, penalty=req.penalty,
+                    temperature=req.temperature, top_p=req.top_p, seed=req.seed,
+                    top_k=req.top_k, min_p=req.min_p, penalty_last_n=req.penalty_last_n,
+                    grammar=bool(req.grammar)) for r, req, slot, _ in items]
+                try:
+                    llm.prefill_batch(segs, self.stream)
+                except _lib.MxError as e:
+                    if e.rc != _lib.MX_ERR_ARG:
+                        raise
+                    # refused as a whole (nothing was enqueued): request by request, so the
+                    # bad one fails alone
+                    for r, req, slot, n0 in items:
+                        if not prefill_one(r, req, slot, n0):
+                            free_slots.add(slot)
+                    continue
+                self.prefill_packs[len(items)] += 1
+                for r, req, slot, n0 in items:
+                    bind(r, req, slot, n0)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                inflight.append((ev, [(r, req, 0) for r, req, _, _ in items]))
+                for r, _, _, _ in items:
+                    if r.issued >= r.limit:
+                        park(r)
+
         def admit():
+            cands: List = []  # packed prefill: the requests this iteration admits
             for r in rows:
                 if not waiting:
-                    return
+                    break
                 if r.req is not None:
                     continue
                 req = waiting.popleft()
@@ -411,9 +502,9 @@ class BatchSynthesizer:
                 if req.grammar and llm.grammar is None:
                     # the context takes its grammar while idle: the first constrained request
                     # waits for the live streams (and, first in line, holds later arrivals)
-                    if any(q.req is not None for q in rows):
+                    if cands or any(q.req is not None for q in rows):
                         waiting.appendleft(req)
-                        return
+                        break
                     for q in rows:
                         park(q)
                     try:  # a vocabulary that cannot hold the preset fails this request alone
@@ -428,32 +519,24 @@ class BatchSynthesizer:
                     req.noise_seed = (self.seed * 1000003 + self._admitted) & _MASK48
                 self._admitted += 1
                 slot = min(free_slots)
-                try:  # a request the device rejects fails alone; the loop serves on
+                if not self.packed_prefill:
+                    prefill_one(r, req, slot, n0)
+                    continue
+                try:  # what the device would refuse is refused here, before the pack forms
                     check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
                                  top_k=req.top_k, min_p=req.min_p,
                                  penalty_last_n=req.penalty_last_n)
-                    llm.prefill(slot, r.idx, req.prompt_ids, req.penalty, self.stream,
-                                temperature=req.temperature, top_p=req.top_p, seed=req.seed,
-                                top_k=req.top_k, min_p=req.min_p,
-                                penalty_last_n=req.penalty_last_n, grammar=bool(req.grammar))
-                except (ValueError, _lib.MxError) as e:
-                    if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
-                        raise  # a device failure is not this request's fault
+                    ids = np.asarray(req.prompt_ids, dtype=np.int64)
+                    if ids.min() < 0 or ids.max() >= llm.cfg.vocab:
+                        raise ValueError("prompt id out of vocab")
+                except ValueError as e:
                     req.error = e
                     complete(req)
                     continue
                 free_slots.discard(slot)
-                r.slot = slot
-                r.req, r.sched, r.n0 = req, WindowScheduler(), n0
-                r.limit = max(1, min(req.max_tokens, llm.max_pos - n0))
-                r.issued, r.stopped, r.parked = 1, False, False
-                req.t_admit = now()
-                live.append(req)
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-                inflight.append((ev, [(r, req, 0)]))
-                if r.issued >= r.limit:
-                    park(r)
+                cands.append((r, req, slot, n0))
+            if cands:
+                admit_packs(cands)
 
         def launch_windows(due: List):
             """due: [(req, window index, codes)] -> one SNAC call per frame-count group."""

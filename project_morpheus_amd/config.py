@@ -198,6 +198,14 @@ def grammar_default(environ=None) -> bool:
     return str(env.get("MORPHEUS_MX_GRAMMAR", "")).strip().lower() in ("1", "true", "yes", "on")
 
 
+def packed_prefill_default(environ=None) -> bool:
+    """Whether the batcher admits the requests of one iteration through packed prefills
+    (``LlmEngine.prefill_batch``): MORPHEUS_MX_PACKED_PREFILL=1 (also true / yes / on); unset,
+    or anything else, means off."""
+    env = os.environ if environ is None else environ
+    return str(env.get("MORPHEUS_MX_PACKED_PREFILL", "")).strip().lower() in ("1", "true", "yes", "on")
+
+
 def request_seed(prompt_ids, seed=None) -> int:
     """The seed of one request: ``seed`` if given, else content-derived (CONTENT_SEED=1) or a
     fresh random 64-bit value."""

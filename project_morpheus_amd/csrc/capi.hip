@@ -136,6 +136,14 @@ struct mx_llm {
   int grammar_head = 1;                   // option: steps of constrained rows only run the lm_head
   int win_lo = 0, win_n = 0;              //   over ids [win_lo, win_lo + win_n) (win_n 0: no window fits)
   long long win_heads = 0;                //   lm_head launches issued over it (mx_llm_grammar_window)
+  // packed prefill (mx_llm_prefill_batch): allocated by its first call, behind every other
+  // buffer, so a context that never packs keeps its allocations
+  int32_t* pk_tab = nullptr;              // the call's table: [max_batch] PackSeg, [max_prefill] PackRow
+  int32_t* pk_idx = nullptr;              // [3][max_batch] head rows' slot, position, decode row
+  unsigned long long* pk_best = nullptr;  // [max_batch] argmax keys of the head rows
+  float* pk_h = nullptr;                  // [max_batch][hidden] the segments' last rows
+  float* pk_logits = nullptr;             // [max_batch][vocab] their penalised logits
+  std::vector<int32_t> pk_host;           // host copy of the table (one upload per call)
   bool final = false;
   int max_rows = 0;
   int legacy_gemv = 0;          // option: grid-stride GEMV for R = 1 too (A/B timing)
@@ -896,11 +904,11 @@ static hipError_t enqueue_sampler(mx_llm* x, const float* lg, const int32_t* slo
 // rows of x->logits used.
 // `window`: every row of the launch that commits is constrained, so only the ids a grammar can
 // allow are computed (x->win_lo, x->win_n); otherwise the whole vocabulary, constrained rows masked.
-static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
-                               const int32_t* pos, int R, unsigned long long* best,
-                               int sampler, bool window, hipStream_t st) {
+// (`lg`: where the launch keeps its rows' penalised logits, [R][vocab])
+static hipError_t enqueue_head_at(mx_llm* x, const float* h, const int32_t* slot,
+                                  const int32_t* pos, int R, unsigned long long* best, float* lg,
+                                  int sampler, bool window, hipStream_t st) {
   const auto& c = x->c;
-  float* lg = x->logits + (size_t)(best - x->best) * c.vocab;
   GemvArgs g{};
   attach_ws(x, g);
   nt_cap(x, g, 4, R);
@@ -920,6 +928,13 @@ static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
   hipError_t e = launch_gemv(g, EPI_ARGMAX, true, st);
   if (e != hipSuccess || sampler == SMP_NONE) return e;  // all-greedy steps carry no sampler node
   return enqueue_sampler(x, lg, slot, pos, R, best, sampler, st);
+}
+
+static hipError_t enqueue_head(mx_llm* x, const float* h, const int32_t* slot,
+                               const int32_t* pos, int R, unsigned long long* best,
+                               int sampler, bool window, hipStream_t st) {
+  float* lg = x->logits + (size_t)(best - x->best) * x->c.vocab;
+  return enqueue_head_at(x, h, slot, pos, R, best, lg, sampler, window, st);
 }
 
 // Longest attention span of the next step over rows [0, n_rows) (host mirror of row_pos).
@@ -1087,6 +1102,132 @@ extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* id
   x->row_samples[row] = samples ? 1 : 0;
   x->row_chain[row] = chain ? 1 : 0;
   x->row_origin[row] = origin;
+  return MX_OK;
+}
+
+// Packed prefill: the segments' prompt rows as ONE row set through the layers (each row
+// carries its own slot and position: the qkv epilogue appends K / V there, the attention reads
+// the row's slot up to its position), then one lm_head launch over the segments' last rows, one
+// sampler node, one commit through the rows' remap.  Around them, one launch each: the slots'
+// clear, the per-row / per-segment setup, the window fill (only with a windowed segment), the
+// tail gather + bind, and (kept logits only) their copy to the decode rows' lines.
+extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n_segs,
+                                    void* stream) {
+  if (!x || !segs) return MX_ERR_ARG;
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  const auto& c = x->c;
+  if (n_segs < 1 || n_segs > c.max_batch) MX_FAIL(x, MX_ERR_ARG, "bad n_segs");
+  // every refusal first: a refused call enqueues nothing and changes no host state
+  std::vector<char> slot_used(c.max_slots, 0), row_used(c.max_batch, 0);
+  long long R64 = 0;
+  int max_n = 0, sampler = SMP_NONE;
+  bool any_window = false, all_constrained = x->gram_on;
+  for (int s = 0; s < n_segs; ++s) {
+    const mx_prefill_seg& g = segs[s];
+    const mx_sampling& sp = g.params;
+    const mx_sampling_ext& xe = g.ext;
+    if (!g.ids_host) MX_FAIL(x, MX_ERR_ARG, "segment without ids");
+    if (!(sp.repetition_penalty > 0.f) || !(sp.top_p > 0.f) || sp.temperature < 0.f)
+      MX_FAIL(x, MX_ERR_ARG, "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0");
+    if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
+        xe.penalty_last_n >= PEN_RING)
+      MX_FAIL(x, MX_ERR_ARG,
+              "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255");
+    if (g.slot < 0 || g.slot >= c.max_slots || g.row < 0 || g.row >= c.max_batch)
+      MX_FAIL(x, MX_ERR_ARG, "slot/row out of range");
+    if (slot_used[g.slot] || row_used[g.row])
+      MX_FAIL(x, MX_ERR_ARG, "slot/row named twice in one call");
+    slot_used[g.slot] = row_used[g.row] = 1;
+    if (g.n_ids < 1 || g.n_ids >= c.max_pos) MX_FAIL(x, MX_ERR_ARG, "bad prompt length");
+    R64 += g.n_ids;
+    if (R64 > c.max_prefill) MX_FAIL(x, MX_ERR_ARG, "prompts exceed max_prefill rows");
+    for (int i = 0; i < g.n_ids; ++i)
+      if (g.ids_host[i] < 0 || g.ids_host[i] >= c.vocab)
+        MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
+    max_n = std::max(max_n, g.n_ids);
+    if (sp.temperature > 0.f)
+      sampler = std::max(sampler, (xe.top_k > 0 || xe.min_p > 0.f) ? (int)SMP_CHAIN : (int)SMP_PLAIN);
+    any_window = any_window || xe.penalty_last_n > 0;
+    all_constrained = all_constrained && x->slot_grammar[g.slot];
+  }
+  const int R = (int)R64;
+  hipStream_t st = (hipStream_t)stream;
+  MX_TRY(x, hipSetDevice(x->device));
+  const size_t seg_words = (size_t)c.max_batch * (sizeof(PackSeg) / 4);
+  if (!x->pk_tab) {
+    MX_TRY(x, x->alloc(&x->pk_tab, seg_words + (size_t)c.max_prefill * (sizeof(PackRow) / 4)));
+    MX_TRY(x, x->alloc(&x->pk_idx, (size_t)3 * c.max_batch));
+    MX_TRY(x, x->alloc(&x->pk_best, (size_t)c.max_batch));
+    MX_TRY(x, x->alloc(&x->pk_h, (size_t)c.max_batch * c.hidden));
+    MX_TRY(x, x->alloc(&x->pk_logits, (size_t)c.max_batch * c.vocab));
+  }
+  // the table: the segments, then their rows
+  x->pk_host.assign(seg_words + (size_t)R * (sizeof(PackRow) / 4), 0);
+  PackSeg* hs = reinterpret_cast<PackSeg*>(x->pk_host.data());
+  PackRow* hr = reinterpret_cast<PackRow*>(x->pk_host.data() + seg_words);
+  for (int s = 0, r = 0; s < n_segs; ++s) {
+    const mx_prefill_seg& g = segs[s];
+    PackSeg& t = hs[s];
+    t.slot = g.slot; t.row = g.row; t.first = r; t.n = g.n_ids;
+    // a constrained slot counts its phases from the prompt's end (-1: unconstrained)
+    t.origin = x->gram_on && x->slot_grammar[g.slot] ? g.n_ids : -1;
+    t.top_k = g.ext.top_k; t.last_n = g.ext.penalty_last_n;
+    t.pen = g.params.repetition_penalty; t.temp = g.params.temperature;
+    t.top_p = g.params.top_p < 1.f ? g.params.top_p : 1.f; t.min_p = g.ext.min_p;
+    t.seed_lo = (uint32_t)g.params.seed; t.seed_hi = (uint32_t)(g.params.seed >> 32);
+    for (int i = 0; i < g.n_ids; ++i, ++r)
+      hr[r] = PackRow{g.ids_host[i], g.slot, i, g.ext.penalty_last_n > 0 ? 0 : 1};
+  }
+  const PackSeg* dsegs = reinterpret_cast<const PackSeg*>(x->pk_tab);
+  const PackRow* drows = reinterpret_cast<const PackRow*>(x->pk_tab + seg_words);
+  // (pageable source, as mx_llm_prefill_ex's copy of the caller's ids: the runtime has read it
+  // when the call returns, so the next call may rebuild the table)
+  MX_TRY(x, hipMemcpyAsync(x->pk_tab, x->pk_host.data(), x->pk_host.size() * 4,
+                           hipMemcpyHostToDevice, st));
+  MX_TRY(x, launch_pack_clear(dsegs, n_segs, c.vocab, x->seen, x->recent, st));
+  PackSetupArgs ps{};
+  ps.rows = drows; ps.segs = dsegs; ps.R = R; ps.n_segs = n_segs; ps.embed = x->embed;
+  ps.hidden = c.hidden; ps.vocab = c.vocab; ps.seen = x->seen; ps.h = x->h_pre;
+  ps.pre_slot = x->pre_slot; ps.pre_pos = x->pre_pos; ps.penalty = x->penalty;
+  ps.temp = x->samp_temp; ps.top_p = x->samp_top_p; ps.seed = x->samp_seed;
+  ps.top_k = x->samp_top_k; ps.min_p = x->samp_min_p; ps.last_n = x->last_n;
+  ps.origin = x->gram_on ? x->gram_origin : nullptr;
+  MX_TRY(x, launch_pack_setup(ps, st));
+  // the attention grid is sized by the longest segment; shorter rows leave its later splits
+  RowSet rs{x->h_pre, x->pre_slot, x->pre_pos, R, max_n, att_cpw_auto(x, R, max_n),
+            att_nw_of(x, R, max_n), 0, false};
+  rs.nsplit = (max_n + 32 * rs.nw * rs.cpw - 1) / (32 * rs.nw * rs.cpw);
+  MX_TRY(x, enqueue_layers(x, rs, st, nullptr));
+  if (any_window)
+    MX_TRY(x, launch_pack_window(drows, dsegs, n_segs, c.vocab, x->seen, x->recent, st));
+  int32_t *hslot = x->pk_idx, *hpos = x->pk_idx + c.max_batch, *hrow = x->pk_idx + 2 * c.max_batch;
+  PackTailArgs pt{};
+  pt.segs = dsegs; pt.h = x->h_pre; pt.hidden = c.hidden; pt.head_h = x->pk_h;
+  pt.head_slot = hslot; pt.head_pos = hpos; pt.head_row = hrow; pt.head_best = x->pk_best;
+  pt.row_slot = x->row_slot; pt.row_pos = x->row_pos;
+  MX_TRY(x, launch_pack_tail(pt, n_segs, st));
+  // the window rule of a step (window_of): only when every segment is constrained
+  const bool window = all_constrained && x->grammar_head && x->win_n > 0;
+  MX_TRY(x, enqueue_head_at(x, x->pk_h, hslot, hpos, n_segs, x->pk_best, x->pk_logits, sampler,
+                            window, st));
+  if (x->logits_all || sampler != SMP_NONE)
+    MX_TRY(x, launch_pack_logits(x->logits, x->pk_logits, hrow, n_segs, c.vocab, st));
+  CommitArgs cm{};
+  cm.best = x->pk_best; cm.dst_row = hrow; cm.row_slot = x->row_slot; cm.row_pos = x->row_pos;
+  cm.row_token = x->row_token; cm.seen = x->seen; cm.hist = x->hist_dev; cm.embed = x->embed;
+  cm.h = x->h_dec; cm.hidden = c.hidden; cm.vocab = c.vocab; cm.max_pos = c.max_pos;
+  cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
+  cm.last_n = x->last_n; cm.recent = x->recent;
+  MX_TRY(x, launch_commit(cm, n_segs, st));
+  for (int s = 0; s < n_segs; ++s) {
+    const mx_prefill_seg& g = segs[s];
+    const bool samples = g.params.temperature > 0.f;
+    x->pos_mirror[g.row] = g.n_ids;
+    x->row_active[g.row] = 1;
+    x->row_samples[g.row] = samples ? 1 : 0;
+    x->row_chain[g.row] = samples && (g.ext.top_k > 0 || g.ext.min_p > 0.f) ? 1 : 0;
+    x->row_origin[g.row] = hs[s].origin;
+  }
   return MX_OK;
 }
 

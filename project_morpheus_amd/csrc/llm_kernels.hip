@@ -12,6 +12,7 @@
 #include "mx_common.h"
 #include "mx_llm_kernels.h"
 
+#include <algorithm>
 #include <initializer_list>
 
 namespace mx {
@@ -1307,6 +1308,142 @@ hipError_t launch_embed_rows(const int32_t* ids, int n, int slot, const uint16_t
 hipError_t launch_scatter_rows(void* dst, const void* src, const int32_t* dmap, int rows,
                                int cols, int mode, hipStream_t st) {
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(rows), dim3(256), 0, st, dst, src, dmap, cols, mode);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// Packed prefill (mx_llm_prefill_batch): the launches around the layers.  Every kernel reads
+// the call's segment / row table (PackSeg, PackRow) from device memory.
+// ---------------------------------------------------------------------------------
+// Every prefill starts its slot clean: zero the slot's seen bytes and penalty ring.  Grid
+// (x, segment), block 256 = PEN_RING.  A slot's bytes start at slot * vocab, any alignment:
+// bytes up to the first 16-byte boundary and past the last one are stored singly by block 0.
+__global__ __launch_bounds__(256) void pack_clear_kernel(const PackSeg* segs, int vocab,
+                                                         uint8_t* seen, int32_t* recent) {
+  const int slot = segs[blockIdx.y].slot;
+  uint8_t* p = seen + (size_t)slot * vocab;
+  const int head = min(vocab, (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15));
+  const int body = (vocab - head) >> 4;  // whole 16-byte units
+  const int tail0 = head + (body << 4);
+  uint4* b = reinterpret_cast<uint4*>(p + head);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < body; i += gridDim.x * 256)
+    b[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (blockIdx.x == 0) {
+    if ((int)threadIdx.x < head) p[threadIdx.x] = 0;
+    if ((int)threadIdx.x < vocab - tail0) p[tail0 + threadIdx.x] = 0;  // < 16 bytes
+    recent[(size_t)slot * PEN_RING + threadIdx.x] = 0;
+  }
+}
+
+hipError_t launch_pack_clear(const PackSeg* segs, int n_segs, int vocab, uint8_t* seen,
+                             int32_t* recent, hipStream_t st) {
+  static_assert(PEN_RING == 256, "pack_clear_kernel: one thread per ring cell");
+  const int gx = std::max(1, std::min(8, (vocab / 16 + 255) / 256));
+  hipLaunchKernelGGL(pack_clear_kernel, dim3(gx, n_segs), dim3(256), 0, st, segs, vocab, seen,
+                     recent);
+  return hipGetLastError();
+}
+
+// Blocks [0, R): row r of the packed row set -- its (slot, position), h[r] = embed[id], and
+// seen[slot][id] = 1 for rows of whole-sequence segments (same-value byte stores from many
+// blocks, as embed_rows_kernel; windowed segments are counted by pack_window_kernel).
+// Blocks [R, R + n_segs): thread 0 writes the segment's slot parameters, extras and origin.
+__global__ __launch_bounds__(256) void pack_setup_kernel(PackSetupArgs a) {
+  const int b = blockIdx.x;
+  if (b >= a.R) {
+    if (threadIdx.x != 0) return;
+    const PackSeg s = a.segs[b - a.R];
+    a.penalty[s.slot] = s.pen;
+    a.temp[s.slot] = s.temp;
+    a.top_p[s.slot] = s.top_p;
+    a.seed[2 * s.slot] = s.seed_lo;
+    a.seed[2 * s.slot + 1] = s.seed_hi;
+    a.top_k[s.slot] = s.top_k;
+    a.min_p[s.slot] = s.min_p;
+    a.last_n[s.slot] = s.last_n;
+    if (a.origin) a.origin[s.slot] = s.origin;
+    return;
+  }
+  const PackRow row = a.rows[b];
+  if (threadIdx.x == 0) {
+    a.pre_slot[b] = row.slot;
+    a.pre_pos[b] = row.pos;
+    if (row.mark) a.seen[(size_t)row.slot * a.vocab + row.id] = 1;
+  }
+  const uint4* e = reinterpret_cast<const uint4*>(a.embed + (size_t)row.id * a.hidden);
+  float4* out = reinterpret_cast<float4*>(a.h + (size_t)b * a.hidden);
+  for (int c = threadIdx.x; c < (a.hidden >> 3); c += 256) {
+    const uint4 w = e[c];
+    out[2 * c] = make_float4(bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y));
+    out[2 * c + 1] = make_float4(bf16_lo(w.z), bf16_hi(w.z), bf16_lo(w.w), bf16_hi(w.w));
+  }
+}
+
+hipError_t launch_pack_setup(const PackSetupArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(pack_setup_kernel, dim3(a.R + a.n_segs), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// window_prefill_kernel for every windowed segment of a pack: block s, thread 0 walks the
+// segment's last min(n, N) ids serially (the slot's bytes and ring were zeroed by pack_clear).
+__global__ __launch_bounds__(64) void pack_window_kernel(const PackRow* rows, const PackSeg* segs,
+                                                         int vocab, uint8_t* seen,
+                                                         int32_t* recent) {
+  if (threadIdx.x != 0) return;
+  const PackSeg s = segs[blockIdx.x];
+  if (s.last_n <= 0) return;
+  int32_t* ring = recent + (size_t)s.slot * PEN_RING;
+  uint8_t* cnt = seen + (size_t)s.slot * vocab;
+  for (int p = max(0, s.n - s.last_n); p < s.n; ++p) {
+    const int tok = rows[s.first + p].id;
+    ++cnt[tok];
+    ring[p & (PEN_RING - 1)] = tok;
+  }
+}
+
+hipError_t launch_pack_window(const PackRow* rows, const PackSeg* segs, int n_segs, int vocab,
+                              uint8_t* seen, int32_t* recent, hipStream_t st) {
+  hipLaunchKernelGGL(pack_window_kernel, dim3(n_segs), dim3(64), 0, st, rows, segs, vocab, seen,
+                     recent);
+  return hipGetLastError();
+}
+
+// The tail's inputs: segment s's last prompt row, with its slot and position n - 1, becomes
+// row s of the contiguous head input; its decode row is bound to (slot, n - 1), which the
+// commit advances to n.  Grid n_segs, block 256.
+__global__ __launch_bounds__(256) void pack_tail_kernel(PackTailArgs a) {
+  const int k = blockIdx.x;
+  const PackSeg s = a.segs[k];
+  const float4* src = reinterpret_cast<const float4*>(a.h + (size_t)(s.first + s.n - 1) * a.hidden);
+  float4* dst = reinterpret_cast<float4*>(a.head_h + (size_t)k * a.hidden);
+  for (int c = threadIdx.x; c < (a.hidden >> 2); c += 256) dst[c] = src[c];
+  if (threadIdx.x == 0) {
+    a.head_slot[k] = s.slot;
+    a.head_pos[k] = s.n - 1;
+    a.head_row[k] = s.row;
+    a.head_best[k] = 0ull;
+    a.row_slot[s.row] = s.slot;
+    a.row_pos[s.row] = s.n - 1;
+  }
+}
+
+hipError_t launch_pack_tail(const PackTailArgs& a, int n_segs, hipStream_t st) {
+  hipLaunchKernelGGL(pack_tail_kernel, dim3(n_segs), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void pack_logits_kernel(float* dst, const float* src,
+                                                          const int32_t* rows, int V) {
+  const int k = blockIdx.y;
+  const float* s = src + (size_t)k * V;
+  float* d = dst + (size_t)rows[k] * V;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) d[i] = s[i];
+}
+
+hipError_t launch_pack_logits(float* dst, const float* src, const int32_t* rows, int n_segs,
+                              int V, hipStream_t st) {
+  const int gx = std::max(1, std::min(64, (V + 1023) / 1024));
+  hipLaunchKernelGGL(pack_logits_kernel, dim3(gx, n_segs), dim3(256), 0, st, dst, src, rows, V);
   return hipGetLastError();
 }
 

@@ -223,6 +223,64 @@ hipError_t launch_embed_rows(const int32_t* ids, int n, int slot, const uint16_t
                              int hidden, int vocab, uint8_t* seen, float* h, hipStream_t st);
 hipError_t launch_scatter_rows(void* dst, const void* src, const int32_t* dmap, int rows,
                                int cols, int mode, hipStream_t st);
+
+// ---- packed prefill (mx_llm_prefill_batch): several prompts as one row set -----------
+// The host uploads one table per call: a PackSeg per segment, then a PackRow per prompt row
+// (segment after segment).  Every kernel below reads it from device memory.
+struct PackSeg {
+  int32_t slot, row;       // KV slot, decode row the stream is bound to
+  int32_t first, n;        // the segment's rows: [first, first + n) of the row set
+  int32_t origin;          // grammar origin of the slot (n, or -1: unconstrained)
+  int32_t top_k, last_n;   // extras (0 = neutral)
+  float pen, temp, top_p, min_p;
+  uint32_t seed_lo, seed_hi;
+  int32_t pad[3];
+};
+static_assert(sizeof(PackSeg) == 64, "PackSeg is uploaded as 16 words");
+struct PackRow {
+  int32_t id, slot, pos;
+  int32_t mark;            // 1: whole-sequence penalty, the row marks seen[slot][id]
+};
+static_assert(sizeof(PackRow) == 16, "PackRow is uploaded as 4 words");
+struct PackSetupArgs {
+  const PackRow* rows;
+  const PackSeg* segs;
+  int R, n_segs;
+  const uint16_t* embed;
+  int hidden, vocab;
+  uint8_t* seen;           // [slots][vocab]
+  float* h;                // [R][hidden] prompt rows (h_pre)
+  int32_t *pre_slot, *pre_pos;
+  // per KV slot generation state, written for every segment's slot
+  float *penalty, *temp, *top_p;
+  uint32_t* seed;
+  int32_t* top_k;
+  float* min_p;
+  int32_t* last_n;
+  int32_t* origin;         // null: the context has no grammar
+};
+struct PackTailArgs {
+  const PackSeg* segs;
+  const float* h;          // [R][hidden] prompt rows after the layers
+  int hidden;
+  float* head_h;           // [n_segs][hidden] the segments' last rows, contiguous
+  int32_t *head_slot, *head_pos, *head_row;  // [n_segs] (head_row: the commit's dst_row)
+  unsigned long long* head_best;             // [n_segs], zeroed
+  int32_t *row_slot, *row_pos;               // decode rows: bound to (slot, n - 1)
+};
+// zero the seen bytes and the penalty ring of every segment's slot (one launch)
+hipError_t launch_pack_clear(const PackSeg* segs, int n_segs, int vocab, uint8_t* seen,
+                             int32_t* recent, hipStream_t st);
+// per row: pre_slot / pre_pos, the embedding gather and the seen mark; per segment: the slot's
+// generation parameters, extras and grammar origin (one launch, grid R + n_segs)
+hipError_t launch_pack_setup(const PackSetupArgs& a, hipStream_t st);
+// window counts and ring of every windowed segment (last_n > 0; one block each, serial)
+hipError_t launch_pack_window(const PackRow* rows, const PackSeg* segs, int n_segs, int vocab,
+                              uint8_t* seen, int32_t* recent, hipStream_t st);
+hipError_t launch_pack_tail(const PackTailArgs& a, int n_segs, hipStream_t st);
+// dst[rows[k]][0, V) = src[k][0, V): the kept logits to the decode rows' own lines
+hipError_t launch_pack_logits(float* dst, const float* src, const int32_t* rows, int n_segs,
+                              int V, hipStream_t st);
 hipError_t launch_to_f32(float* dst, const void* src, int64_t n, int src_bf16, hipStream_t st);
 // [N][K] (esz bytes per element) -> fragment-major copy for the multi-row GEMM (mx_rows_v4.inc)
 hipError_t launch_frag_major(const void* src, void* dst, int N, int K, int esz, hipStream_t st);

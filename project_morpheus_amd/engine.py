@@ -40,6 +40,22 @@ def _dtype_code(t: torch.Tensor) -> int:
     raise TypeError(f"unsupported weight dtype {t.dtype}")
 
 
+@dataclass
+class PrefillSegment:
+    """One stream of ``LlmEngine.prefill_batch``: ``prefill``'s arguments as fields."""
+    slot: int
+    row: int
+    ids: Sequence[int]
+    penalty: float = 1.1
+    temperature: float = 0.0
+    top_p: float = 1.0
+    seed: int = 0
+    top_k: int = 0
+    min_p: float = 0.0
+    penalty_last_n: int = 0
+    grammar: bool = False
+
+
 class LlmEngine:
     """One mx_llm context on one GPU (weights replicated per GPU)."""
 
@@ -106,6 +122,31 @@ class LlmEngine:
         self._check(self.lib.mx_llm_prefill_ex(self.h, slot, row, arr.ctypes.data, len(arr),
                                                C.byref(sp), C.byref(ext),
                                                C.c_void_p(stream.cuda_stream)))
+
+    def prefill_batch(self, segments: Sequence, stream) -> None:
+        """Packed prefill (mx_llm_prefill_batch): admit several streams in one pass over the
+        weights.  ``segments``: ``PrefillSegment`` objects or dicts with ``slot``, ``row``,
+        ``ids``, ``penalty`` and any of ``prefill``'s keywords.  Leaves the engine as the same
+        ``prefill`` calls in order would; a call the device refuses changes nothing."""
+        segs = [s if isinstance(s, PrefillSegment) else PrefillSegment(**s) for s in segments]
+        for s in segs:
+            if bool(s.grammar) != self._slot_grammar.get(s.slot, False) and \
+                    0 <= s.slot < self.max_slots:
+                self._check(self.lib.mx_llm_set_slot_grammar(self.h, s.slot, int(bool(s.grammar))))
+                self._slot_grammar[s.slot] = bool(s.grammar)
+        arr = (_lib.PrefillSeg * max(1, len(segs)))()
+        keep = []  # the id arrays live until the call returns
+        for a, s in zip(arr, segs):
+            ids = np.ascontiguousarray(np.asarray(s.ids, dtype=np.int32))
+            keep.append(ids)
+            a.slot, a.row, a.ids_host, a.n_ids = int(s.slot), int(s.row), ids.ctypes.data, len(ids)
+            a.params = _lib.Sampling(temperature=float(s.temperature), top_p=float(s.top_p),
+                                     repetition_penalty=float(s.penalty),
+                                     seed=int(s.seed) & (2**64 - 1))
+            a.ext = _lib.SamplingExt(top_k=int(s.top_k), min_p=float(s.min_p),
+                                     penalty_last_n=int(s.penalty_last_n))
+        self._check(self.lib.mx_llm_prefill_batch(self.h, arr, len(segs),
+                                                  C.c_void_p(stream.cuda_stream)))
 
     def decode(self, n_rows: int, stream) -> None:
         """One step for rows [0, n_rows), each under its slot's generation parameters."""

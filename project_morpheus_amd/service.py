@@ -35,9 +35,12 @@ class Service:
     def __init__(self, device: int = C.MX_DEVICE, cfg: Optional[C.OrpheusConfig] = None,
                  llm_weights=None, snac_weights=None, max_pos: int = 2048,
                  tokenizer: Optional[Tokenizer] = None, max_prefill: int = 512,
-                 max_batch: int = C.MX_MAX_SLOTS, synthetic_audio: Optional[bool] = None):
+                 max_batch: int = C.MX_MAX_SLOTS, synthetic_audio: Optional[bool] = None,
+                 packed_prefill: Optional[bool] = None):
         """``synthetic_audio``: feed the SNAC schedule a seeded audio-code stream per request
-        (default: whenever the LLM weights are synthetic, which never speak)."""
+        (default: whenever the LLM weights are synthetic, which never speak).
+        ``packed_prefill``: admit the requests of one loop iteration through packed prefills
+        (None: MORPHEUS_MX_PACKED_PREFILL, off when unset)."""
         torch.cuda.set_device(device)
         synthetic = False
         if cfg is None:
@@ -58,7 +61,7 @@ class Service:
                              max_pos=max_pos, max_batch=max_batch, max_prefill=max_prefill)
         del llm_weights
         self.snac = SnacDecoder(snac_weights, device=device, max_batch=max_batch)
-        self.batch = BatchSynthesizer(self.llm, self.snac).start()
+        self.batch = BatchSynthesizer(self.llm, self.snac, packed_prefill=packed_prefill).start()
         self.tok = tokenizer or default_tokenizer()
 
     @classmethod
