@@ -148,6 +148,54 @@ static_assert(sizeof(void*) != 8 ||
               "mx_prefill_seg layout");
 #endif
 int mx_llm_prefill_batch(mx_llm* ctx, const mx_prefill_seg* segs, int n_segs, void* stream);
+/* Prompt continuation (DESIGN.md §3 "Prompt continuation"): a prompt given as chunks
+ * c_0 .. c_m, chunk c_j at pos0 = |c_0| + .. + |c_{j-1}| and the last one marked `last`, leaves
+ * the slot, the row, the penalty state, the grammar origin and the sampler counters as ONE
+ * prefill of the concatenated ids would, up to float summation order inside the layer kernels
+ * and the bf16 KV rounding that follows from it.  A chunk with last = 0 records its ids in the
+ * slot's id history, runs the layers and appends K / V: no head, sampler or commit, no row bound,
+ * `row`, `params` and `ext` not read.  The chunk with last = 1 builds the penalty state from the
+ * history over [0, pos0 + n_ids) (whole sequence, or the window of the last N positions, which may
+ * straddle a seam), sets the grammar origin to pos0 + n_ids, picks the first token (Philox
+ * counter of position pos0 + n_ids) and binds `row` there.  pos0 = 0 with last = 1 is
+ * mx_llm_prefill_ex; pos0 = 0 starts the slot over.
+ * The library mirrors on the host how many prompt positions every slot holds (mx_llm_slot_len;
+ * set by every prefill entry point and by mx_llm_fork_slot).  Every check runs before anything
+ * is enqueued, so a refused call leaves the context as it was: MX_ERR_ARG on a slot (or, last,
+ * a row) out of range, n_ids outside [1, max_prefill], pos0 < 0 or pos0 + n_ids >= max_pos, an id
+ * out of vocab, sampling values mx_llm_prefill_ex refuses (last only), or a context one attention
+ * launch cannot merge; MX_ERR_STATE on pos0 > 0 that is not the slot's length, on a slot bound to
+ * an active row, and before finalize.
+ * Layout (64-bit ABI): offset 0 slot, 4 row, 8 ids_host, 16 n_ids, 20 pos0, 24 last,
+ *   32 params (24 bytes), 56 ext (12 bytes); sizeof 72. */
+typedef struct mx_prefill_chunk {
+  int32_t slot, row;          /* row is read only when last != 0 */
+  const int32_t* ids_host;
+  int32_t n_ids;
+  int32_t pos0;               /* positions the slot already holds */
+  int32_t last;               /* 0: layers + KV only; 1: ends the prompt */
+  mx_sampling params;         /* read only when last != 0 */
+  mx_sampling_ext ext;
+} mx_prefill_chunk;
+#ifdef __cplusplus
+static_assert(sizeof(void*) != 8 ||
+                  (sizeof(mx_prefill_chunk) == 72 && offsetof(mx_prefill_chunk, ids_host) == 8 &&
+                   offsetof(mx_prefill_chunk, n_ids) == 16 && offsetof(mx_prefill_chunk, pos0) == 20 &&
+                   offsetof(mx_prefill_chunk, last) == 24 && offsetof(mx_prefill_chunk, params) == 32 &&
+                   offsetof(mx_prefill_chunk, ext) == 56),
+              "mx_prefill_chunk layout");
+#endif
+int mx_llm_prefill_chunk(mx_llm* ctx, const mx_prefill_chunk* chunk, void* stream);
+/* Fork: `dst_slot` holds `src_slot`'s first n_pos positions afterwards -- K / V of every layer
+ * (one device copy, ordered on `stream`) and the id history; no penalty state (the request's
+ * final chunk builds it).  `src_slot` may be an unbound template slot or bound to a live row:
+ * its first n_pos <= mx_llm_slot_len positions are immutable.  MX_ERR_STATE (nothing enqueued,
+ * nothing changed) on a slot out of range, dst == src, n_pos < 1 or above the source's length,
+ * or a dst bound to an active row. */
+int mx_llm_fork_slot(mx_llm* ctx, int dst_slot, int src_slot, int n_pos, void* stream);
+/* The host mirror: prompt positions `slot` holds (its last prefill's length, the chunks so far,
+ * or a fork's n_pos; tokens decoded behind the prompt are not counted). */
+int mx_llm_slot_len(const mx_llm* ctx, int slot, int* n_pos);
 /* One decode step for rows [0, n_rows), each under its slot's parameters (hipGraph-captured
  * per row count and attention grid; replayed). */
 int mx_llm_decode(mx_llm* ctx, int n_rows, void* stream);

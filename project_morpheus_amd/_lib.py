@@ -62,6 +62,13 @@ class PrefillSeg(C.Structure):
                 ("n_ids", C.c_int32), ("params", Sampling), ("ext", SamplingExt)]
 
 
+class PrefillChunk(C.Structure):
+    """mx_prefill_chunk: one chunk of a prompt behind ``pos0`` positions (mx_llm_prefill_chunk)."""
+    _fields_ = [("slot", C.c_int32), ("row", C.c_int32), ("ids_host", C.c_void_p),
+                ("n_ids", C.c_int32), ("pos0", C.c_int32), ("last", C.c_int32),
+                ("params", Sampling), ("ext", SamplingExt)]
+
+
 class CodeGrammar(C.Structure):
     """mx_code_grammar: ids [code_base + k*codes + code_min, code_base + (k+1)*codes) at phase k,
     plus stop_id at phase 0."""
@@ -81,6 +88,9 @@ _SIGS = {
     "mx_llm_prefill_ex": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(Sampling),
                                     C.POINTER(SamplingExt), _P]),
     "mx_llm_prefill_batch": (C.c_int, [_P, C.POINTER(PrefillSeg), C.c_int, _P]),
+    "mx_llm_prefill_chunk": (C.c_int, [_P, C.POINTER(PrefillChunk), _P]),
+    "mx_llm_fork_slot": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "mx_llm_slot_len": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "mx_llm_decode": (C.c_int, [_P, C.c_int, _P]),
     "mx_llm_check": (C.c_int, [_P, _P]),
     "mx_llm_decode_profiled": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_double), C.c_int]),

@@ -34,13 +34,17 @@ _END = object()
 
 
 def _default_source(prompt: str, voice: str, use_batching: bool, max_batch_chars: int,
-                    cancel: threading.Event, grammar: Optional[bool] = None) -> Iterator[bytes]:
+                    cancel: threading.Event, grammar: Optional[bool] = None,
+                    prefix: Optional[str] = None) -> Iterator[bytes]:
     """Every long-form part is submitted at once (they decode as concurrent rows of the
     GPU's batch) and their PCM is yielded in part order.  ``grammar``: the parts decode under
-    the Orpheus code grammar (None: the service's default, MORPHEUS_MX_GRAMMAR)."""
+    the Orpheus code grammar (None: the service's default, MORPHEUS_MX_GRAMMAR).  ``prefix``:
+    every part continues that registered prefix (a cached voice prompt)."""
     from .service import get_service
     svc = get_service()
     kw = {} if grammar is None else {"grammar": bool(grammar)}
+    if prefix is not None:
+        kw["prefix"] = prefix
     handles = [svc.submit(part, voice, **kw) for part in
                I.batch_sentences(prompt, max_batch_chars, use_batching)]
     try:
@@ -66,8 +70,10 @@ class MxTTSAdapter:
 
     def __init__(self, prompt: str, voice: str = I.DEFAULT_VOICE, *, use_batching: bool = False,
                  max_batch_chars: int = 1000, pull_unit: Optional[str] = None,
-                 grammar: Optional[bool] = None) -> None:
-        """``grammar``: decode under the Orpheus code grammar (None: MORPHEUS_MX_GRAMMAR).
+                 grammar: Optional[bool] = None, voice_prompt: Optional[str] = None) -> None:
+        """``voice_prompt``: the name of a registered prefix (``Service.register_prefix``, e.g.
+        ``inference.frame_voice_pairs`` of reference speech) the utterance continues.
+        ``grammar``: decode under the Orpheus code grammar (None: MORPHEUS_MX_GRAMMAR).
         ``pull_unit``: "bytes" (the reference contract, default) or "ms" (the unit the
         descriptor declares: ``pull(n)`` returns n ms of PCM); default from
         ``config.PULL_UNIT`` (MORPHEUS_MX_PULL_UNIT)."""
@@ -77,6 +83,9 @@ class MxTTSAdapter:
         self.use_batching = use_batching
         self.max_batch_chars = max_batch_chars
         self.grammar = grammar
+        if voice_prompt is not None and (not isinstance(voice_prompt, str) or not voice_prompt):
+            raise ValueError(f"voice_prompt must be a non-empty string, got {voice_prompt!r}")
+        self.voice_prompt = voice_prompt
         unit = pull_unit or PULL_UNIT
         if unit not in ("bytes", "ms"):
             raise ValueError(f"pull_unit must be 'bytes' or 'ms', got {unit!r}")
@@ -95,6 +104,8 @@ class MxTTSAdapter:
         cancel = threading.Event()
         # (an injected source keeps the five-argument form unless a grammar choice was made)
         kw = {} if self.grammar is None else {"grammar": self.grammar}
+        if self.voice_prompt is not None:
+            kw["prefix"] = self.voice_prompt
         src = self.source(self.prompt, self.voice, self.use_batching, self.max_batch_chars,
                           cancel, **kw)
 

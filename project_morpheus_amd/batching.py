@@ -80,6 +80,8 @@ class StreamRequest:
     on_done: Optional[Callable[["StreamRequest"], None]] = None
     on_token: Optional[Callable[["StreamRequest", int], None]] = None
     audio: bool = True                      # False: token stream only (no SNAC windows)
+    prefix: Optional[str] = None            # a registered prefix (register_prefix): prompt_ids
+                                            # is then the suffix behind it
     # filled in by the synthesizer
     tokens: List[int] = field(default_factory=list)
     pcm: List[bytes] = field(default_factory=list)  # for callers that collect chunks here
@@ -137,6 +139,17 @@ def check_params(penalty: float, temperature: float, top_p: float, max_tokens: i
         raise ValueError(f"max_tokens must be a positive integer, got {max_tokens!r}")
 
 
+class UnknownPrefix(ValueError):
+    """A request names a prefix nobody registered (HTTP 400 on the completions surface)."""
+
+
+def check_prefix(prefix) -> None:
+    """A request's ``prefix`` is None or the non-empty name of a registered prefix (whether it
+    is registered is the loop's to say: an unknown name fails that request alone)."""
+    if prefix is not None and (not isinstance(prefix, str) or not prefix):
+        raise ValueError(f"prefix must be a non-empty string, got {prefix!r}")
+
+
 class _Row:
     """One stream's decode state; ``idx`` is the device row it decodes in (rows are compacted,
     so it can change), ``slot`` its KV slot (fixed for the stream's life)."""
@@ -151,6 +164,9 @@ class _Row:
         self.limit = 0       # tokens this row may issue (max_tokens clipped to max_pos)
         self.parked = False  # released on the device (all tokens issued / stopped)
         self.stopped = False
+        # mid-prompt (a long or prefixed prompt): [positions the slot holds before prompt_ids,
+        # the chunks still to enqueue]; the row is reserved and stays parked until the final one
+        self.prompt: Optional[list] = None
 
 
 def plan_compaction(rows: List[_Row]) -> List[Tuple[int, int]]:
@@ -193,6 +209,107 @@ def plan_prefill_packs(lengths: Sequence[int], max_prefill: int, max_k: int) -> 
     if cur:
         packs.append(cur)
     return packs
+
+
+def plan_prompt_chunks(n: int, pos0: int, max_prefill: int) -> List[Tuple[int, int, bool]]:
+    """Chunks of ``n`` prompt ids that go behind the ``pos0`` positions a slot already holds, for
+    ``LlmEngine.prefill_chunk``: ``(offset, length, last)`` in order, ``offset`` into the ids (the
+    chunk's ``pos0`` is ``pos0 + offset``).  Every chunk but the last is ``max_prefill`` long;
+    only the last is marked."""
+    if n < 1 or pos0 < 0 or max_prefill < 1:
+        raise ValueError(f"bad chunk plan: n {n}, pos0 {pos0}, max_prefill {max_prefill}")
+    out = []
+    for off in range(0, n, max_prefill):
+        length = min(max_prefill, n - off)
+        out.append((off, length, off + length == n))
+    return out
+
+
+class PrefixHandle:
+    """Outcome of ``register_prefix`` / ``unregister_prefix``: completes once the loop thread has
+    enqueued the prefix (every later request is ordered behind it) or refused it."""
+
+    def __init__(self, name: str):
+        self.name = name
+        self.error: Optional[BaseException] = None
+        self._ev = threading.Event()
+
+    def _finish(self, error: Optional[BaseException] = None) -> None:
+        self.error = error
+        self._ev.set()
+
+    @property
+    def done(self) -> bool:
+        return self._ev.is_set()
+
+    def wait(self, timeout: Optional[float] = None) -> bool:
+        return self._ev.wait(timeout)
+
+    def result(self, timeout: Optional[float] = None) -> str:
+        """The prefix's name once it is registered; raises what refused it."""
+        if not self._ev.wait(timeout):
+            raise TimeoutError(f"prefix {self.name!r} not registered yet")
+        if self.error is not None:
+            raise self.error
+        return self.name
+
+
+class _Prefix:
+    def __init__(self, name: str, slot: int, ids: Sequence[int]):
+        self.name, self.slot, self.ids, self.n = name, slot, list(ids), len(ids)
+        self.ready = False        # every chunk enqueued: requests may fork it
+        self.pins = 0             # requests in admission that named it
+        self.plan: Deque = deque()
+        self.handle: Optional[PrefixHandle] = None
+
+
+class PrefixRegistry:
+    """Names -> template KV slots, least recently used first.  Pure host bookkeeping: the caller
+    prefills and forks."""
+
+    def __init__(self, slots: Sequence[int]):
+        self.free: List[int] = sorted(slots)
+        self.entries: "collections.OrderedDict[str, _Prefix]" = collections.OrderedDict()
+
+    def __contains__(self, name) -> bool:
+        return name in self.entries
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def get(self, name, touch: bool = True) -> Optional[_Prefix]:
+        p = self.entries.get(name)
+        if p is not None and touch:
+            self.entries.move_to_end(name)
+        return p
+
+    def place(self, name: str, ids: Sequence[int]) -> Tuple[_Prefix, Optional[_Prefix]]:
+        """A template slot for ``name`` -> (its new entry, the entry it displaced or None): the
+        name's own slot if it is registered already, else a free one, else that of the least
+        recently used prefix that is ready and that no request in admission names.  RuntimeError
+        when there is none."""
+        old = self.entries.pop(name, None)
+        if old is not None:
+            slot = old.slot
+        elif self.free:
+            slot = self.free.pop(0)
+        else:
+            old = next((p for p in self.entries.values() if p.ready and p.pins == 0), None)
+            if old is None:
+                raise RuntimeError("no template slot for a prefix "
+                                   f"({len(self.entries)} registered, none can be evicted)")
+            del self.entries[old.name]
+            slot = old.slot
+        p = _Prefix(name, slot, ids)
+        self.entries[name] = p
+        return p, old
+
+    def remove(self, name: str) -> Optional[_Prefix]:
+        p = self.entries.pop(name, None)
+        if p is not None:
+            self.free.append(p.slot)
+            self.free.sort()
+        return p
 
 
 class _BatchRing:
@@ -263,10 +380,20 @@ class TokenHandle(StreamHandle):
 class BatchSynthesizer:
     def __init__(self, llm: LlmEngine, snac: SnacDecoder, depth: Optional[int] = None, seed: int = 0,
                  snac_min_batch: Optional[int] = None, snac_max_hold: Optional[int] = None,
-                 compact: bool = True, packed_prefill: Optional[bool] = None):
-        if llm.max_slots < llm.max_batch:
-            raise ValueError("BatchSynthesizer needs one KV slot per decode row")
+                 compact: bool = True, packed_prefill: Optional[bool] = None,
+                 prefix_slots: int = 0):
+        if llm.max_slots - prefix_slots < llm.max_batch or prefix_slots < 0:
+            raise ValueError("BatchSynthesizer needs one KV slot per decode row"
+                             + (f" below its {prefix_slots} template slots" if prefix_slots else ""))
         self.llm, self.snac, self.seed = llm, snac, seed
+        # prefix cache: the engine's last `prefix_slots` KV slots hold registered prefixes
+        # (templates); a request naming one starts as a fork of it
+        self.prefix_slots = prefix_slots
+        self.prefixes = PrefixRegistry(range(llm.max_slots - prefix_slots, llm.max_slots))
+        self.prefix_fills = collections.Counter()   # times a name's prefix was prefilled
+        self.prefix_forks = collections.Counter()   # requests started from a name's prefix
+        self.prompt_chunks = 0                      # prefill_chunk calls of long / prefixed prompts
+        self._ctl: Deque = deque()                  # (op, name, ids, handle) for the loop thread
         self.compact = compact  # row compaction (mx_llm_move_row) when streams end
         self.row_steps = collections.Counter()  # decode steps issued per row count (stats)
         # packed prefill: the requests one iteration admits go through LlmEngine.prefill_batch,
@@ -337,6 +464,7 @@ class BatchSynthesizer:
     def submit(self, req: StreamRequest) -> StreamHandle:
         check_params(req.penalty, req.temperature, req.top_p, req.max_tokens, top_k=req.top_k,
                      min_p=req.min_p, penalty_last_n=req.penalty_last_n)
+        check_prefix(req.prefix)
         if self._thread is None:
             self.start()
         h = StreamHandle(req) if req.audio else TokenHandle(req)
@@ -349,6 +477,45 @@ class BatchSynthesizer:
                 raise RuntimeError("BatchSynthesizer stopped")
             self._inbox.append(req)
             self.outstanding_tokens += req.max_tokens
+            self._cv.notify()
+        return h
+
+    def register_prefix(self, name: str, ids: Sequence[int]) -> PrefixHandle:
+        """Prefill ``ids`` once into a template slot under ``name`` (replacing an earlier prefix
+        of that name); requests with ``StreamRequest.prefix == name`` then start as a fork of it.
+        Goes through the loop thread like a request, chunked like a long prompt; with no free
+        template slot the least recently used prefix is evicted.  The handle completes, or
+        carries the error."""
+        h = PrefixHandle(name)
+        try:
+            if not isinstance(name, str) or not name:
+                raise ValueError(f"prefix name must be a non-empty string, got {name!r}")
+            ids = [int(t) for t in ids]
+            if self.prefix_slots < 1:
+                raise ValueError("no template slots (prefix_slots is 0)")
+            if not 1 <= len(ids) < self.llm.max_pos - 1:
+                raise ValueError(f"prefix of {len(ids)} ids does not fit (max_pos "
+                                 f"{self.llm.max_pos}: it needs room for a suffix and a token)")
+            if min(ids) < 0 or max(ids) >= self.llm.cfg.vocab:
+                raise ValueError("prefix id out of vocab")
+        except (TypeError, ValueError) as e:
+            h._finish(e)
+            return h
+        with self._cv:
+            self._ctl.append(("register", name, ids, h))
+            self._cv.notify()
+        return h
+
+    def has_prefix(self, name) -> bool:
+        """``name`` is registered, or its registration is on its way to the loop thread."""
+        with self._cv:
+            return name in self.prefixes or any(op == "register" and n == name
+                                                for op, n, _, _ in self._ctl)
+
+    def unregister_prefix(self, name: str) -> PrefixHandle:
+        h = PrefixHandle(name)
+        with self._cv:
+            self._ctl.append(("unregister", name, None, h))
             self._cv.notify()
         return h
 
@@ -369,7 +536,7 @@ class BatchSynthesizer:
 
         def idle(now):
             with self._cv:
-                if not self._inbox and not self._stop:
+                if not self._inbox and not self._ctl and not self._stop:
                     self._cv.wait(timeout=0.05)
 
         def done_cb(req):
@@ -383,6 +550,13 @@ class BatchSynthesizer:
                 self._stop = True
                 orphans = list(self._inbox) + list(self._live)
                 self._inbox.clear()
+                ctl = list(self._ctl)
+                self._ctl.clear()
+            for _, _, _, h in ctl:
+                h._finish(e)
+            for p in self.prefixes.entries.values():
+                if p.handle is not None and not p.handle.done:
+                    p.handle._finish(e)
             for req in orphans:
                 req.error = e
                 if req.on_done is not None:
@@ -393,7 +567,7 @@ class BatchSynthesizer:
     def _loop(self, t0: float, poll, idle, finished, done_cb) -> None:
         llm, B = self.llm, self.llm.max_batch
         rows = [_Row(i) for i in range(B)]
-        free_slots = set(range(llm.max_slots))
+        free_slots = set(range(llm.max_slots - self.prefix_slots))  # (templates sit above)
         waiting: Deque[StreamRequest] = deque()
         inflight: Deque = deque()   # (event, [(row, req, k)])
         pending: Deque = deque()    # (event, ring index, [(req, nbytes)])
@@ -425,7 +599,8 @@ class BatchSynthesizer:
             r.limit = max(1, min(req.max_tokens, llm.max_pos - n0))
             r.issued, r.stopped, r.parked = 1, False, False
             req.t_admit = now()
-            live.append(req)
+            if not any(q is req for q in live):
+                live.append(req)
 
         def prefill_one(r: _Row, req: StreamRequest, slot: int, n0: int) -> bool:
             try:  # a request the device rejects fails alone; the loop serves on
@@ -482,6 +657,148 @@ class BatchSynthesizer:
                     if r.issued >= r.limit:
                         park(r)
 
+        def refused(e) -> bool:
+            """A chunk or fork the device refused for its arguments fails its owner alone."""
+            if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
+                raise e  # a device failure is nobody's fault
+            return True
+
+        def control() -> None:
+            """Prefix registrations and removals handed to the loop thread."""
+            while True:
+                with self._cv:
+                    if not self._ctl:
+                        return
+                    op, name, ids, h = self._ctl.popleft()
+                    p, old, err = None, None, None
+                    if op == "unregister":
+                        p = self.prefixes.remove(name)
+                    else:  # (under the lock: has_prefix never sees the name in neither place)
+                        try:
+                            p, old = self.prefixes.place(name, ids)
+                        except RuntimeError as e:
+                            err = e
+                            if any(not q.ready for q in self.prefixes.entries.values()):
+                                # a slot frees up once the prefix being prefilled is ready
+                                self._ctl.appendleft((op, name, ids, h))
+                                return
+                if op == "unregister":
+                    if p is not None and p.handle is not None and not p.handle.done:
+                        p.handle._finish(KeyError(f"prefix {name!r} was unregistered"))
+                    h._finish(None if p is not None else KeyError(f"unknown prefix {name!r}"))
+                    continue
+                if err is not None:
+                    h._finish(err)
+                    continue
+                if old is not None and old.handle is not None and not old.handle.done:
+                    old.handle._finish(KeyError(f"prefix {old.name!r} was replaced"))
+                p.handle = h
+                p.plan = deque(plan_prompt_chunks(p.n, 0, llm.max_prefill))
+
+        def advance_prefixes() -> bool:
+            """One chunk of every prefix still being prefilled; True while one is unfinished."""
+            busy = False
+            for p in [q for q in self.prefixes.entries.values() if not q.ready]:
+                off, n, _ = p.plan.popleft()
+                try:  # every chunk of a template is non-final: layers and KV only
+                    llm.prefill_chunk(p.slot, p.ids[off:off + n], off, self.stream)
+                except (ValueError, _lib.MxError) as e:
+                    refused(e)
+                    self.prefixes.remove(p.name)
+                    p.handle._finish(e)
+                    continue
+                self.prompt_chunks += 1
+                if p.plan:
+                    busy = True
+                    continue
+                p.ready = True
+                self.prefix_fills[p.name] += 1
+                p.handle._finish(None)
+            return busy
+
+        def drop_prompt(r: _Row, e: BaseException) -> None:
+            req = r.req
+            free_slots.add(r.slot)
+            r.req, r.sched, r.stopped, r.parked, r.slot, r.prompt = None, None, False, False, -1, None
+            req.error = e
+            complete(req)
+
+        def start_prompt(r: _Row, req: StreamRequest, slot: int, pre: Optional[_Prefix],
+                         n0: int) -> None:
+            """Reserve row and slot for a prompt that is not one plain prefill: the fork of its
+            prefix now, its chunks from ``advance_prompts`` on."""
+            try:
+                check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
+                             top_k=req.top_k, min_p=req.min_p,
+                             penalty_last_n=req.penalty_last_n)
+                ids = np.asarray(req.prompt_ids, dtype=np.int64)
+                if ids.min() < 0 or ids.max() >= llm.cfg.vocab:
+                    raise ValueError("prompt id out of vocab")
+            except ValueError as e:
+                req.error = e
+                complete(req)
+                return
+            free_slots.discard(slot)
+            r.slot, r.req, r.sched, r.n0 = slot, req, None, n0
+            r.stopped, r.parked = False, True   # parked on the device until the final chunk
+            live.append(req)
+            pos0 = 0
+            if pre is not None:
+                pre.pins += 1
+                try:
+                    llm.fork_slot(slot, pre.slot, pre.n, self.stream)
+                except _lib.MxError as e:
+                    refused(e)
+                    drop_prompt(r, e)
+                    return
+                finally:
+                    pre.pins -= 1
+                self.prefix_forks[pre.name] += 1
+                pos0 = pre.n
+            r.prompt = [pos0, deque(plan_prompt_chunks(len(req.prompt_ids), pos0, llm.max_prefill))]
+
+        def advance_prompts() -> bool:
+            """Every mid-prompt row: its next chunks up to and including ONE non-final chunk (the
+            live streams step between chunks); the final chunk binds the row as prefill_one
+            does.  True while a row is still mid-prompt."""
+            busy = False
+            for r in rows:
+                if r.req is None or r.prompt is None:
+                    continue
+                req = r.req
+                pos0, plan = r.prompt
+                last = False
+                while plan and not last:
+                    off, n, last = plan.popleft()
+                    kw = dict(last=True, row=r.idx, penalty=req.penalty,
+                              temperature=req.temperature, top_p=req.top_p, seed=req.seed,
+                              top_k=req.top_k, min_p=req.min_p,
+                              penalty_last_n=req.penalty_last_n,
+                              grammar=bool(req.grammar)) if last else {}
+                    try:
+                        llm.prefill_chunk(r.slot, req.prompt_ids[off:off + n], pos0 + off,
+                                          self.stream, **kw)
+                    except (ValueError, _lib.MxError) as e:
+                        refused(e)
+                        drop_prompt(r, e)
+                        break
+                    self.prompt_chunks += 1
+                    if not last:
+                        break
+                if r.req is not req:
+                    continue
+                if not last:
+                    busy = True
+                    continue
+                r.prompt = None
+                bind(r, req, r.slot, r.n0)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                inflight.append((ev, [(r, req, 0)]))
+                if r.issued >= r.limit:
+                    park(r)
+            return busy
+
         def admit():
             cands: List = []  # packed prefill: the requests this iteration admits
             for r in rows:
@@ -493,12 +810,27 @@ class BatchSynthesizer:
                 if req.cancelled:
                     complete(req)
                     continue
-                n0 = len(req.prompt_ids)
-                if n0 < 1 or n0 > llm.max_prefill or n0 >= llm.max_pos:
-                    req.error = ValueError(f"prompt of {n0} ids does not fit (max_prefill "
-                                           f"{llm.max_prefill}, max_pos {llm.max_pos})")
+                pre = None
+                if req.prefix is not None:
+                    pre = self.prefixes.get(req.prefix) if isinstance(req.prefix, str) else None
+                    if pre is None and isinstance(req.prefix, str) and self.has_prefix(req.prefix):
+                        waiting.appendleft(req)  # its registration has not reached the loop yet
+                        break
+                    if pre is None:  # an unknown (or evicted) name fails this request alone
+                        req.error = UnknownPrefix(f"unknown prefix {req.prefix!r}")
+                        complete(req)
+                        continue
+                    if not pre.ready:  # still being prefilled: first in line, holds later arrivals
+                        waiting.appendleft(req)
+                        break
+                # n0, limit, the window scheduler and the grammar count from the whole prompt
+                n0 = len(req.prompt_ids) + (pre.n if pre is not None else 0)
+                if len(req.prompt_ids) < 1 or n0 >= llm.max_pos:
+                    req.error = ValueError(f"prompt of {n0} ids does not fit (max_pos "
+                                           f"{llm.max_pos})")
                     complete(req)
                     continue
+                chunked = pre is not None or n0 > llm.max_prefill
                 if req.grammar and llm.grammar is None:
                     # the context takes its grammar while idle: the first constrained request
                     # waits for the live streams (and, first in line, holds later arrivals)
@@ -519,6 +851,9 @@ class BatchSynthesizer:
                     req.noise_seed = (self.seed * 1000003 + self._admitted) & _MASK48
                 self._admitted += 1
                 slot = min(free_slots)
+                if chunked:  # (packed prefill takes only prompts that fit one chunk, no prefix)
+                    start_prompt(r, req, slot, pre, n0)
+                    continue
                 if not self.packed_prefill:
                     prefill_one(r, req, slot, n0)
                     continue
@@ -588,7 +923,7 @@ class BatchSynthesizer:
 
         def finish(r: _Row, due: List):
             req = r.req
-            if not req.cancelled and req.audio:
+            if not req.cancelled and req.audio and r.sched is not None:
                 for win in r.sched.flush():
                     due.append((req, req.windows, win))
                     req.windows += 1
@@ -596,6 +931,7 @@ class BatchSynthesizer:
             closing.append(req)
             free_slots.add(r.slot)
             r.req, r.sched, r.stopped, r.parked, r.slot = None, None, False, False, -1
+            r.prompt = None
 
         def compact():
             """Live rows to a prefix (plan_compaction), so a step runs the row class of the
@@ -620,7 +956,10 @@ class BatchSynthesizer:
             for r in rows:  # barge-in: free cancelled rows now
                 if r.req is not None and r.req.cancelled:
                     finish(r, [])
+            control()
+            busy = advance_prefixes()
             admit()
+            busy = advance_prompts() or busy
             compact()
             act = [r for r in rows if r.req is not None and not r.stopped and not r.parked]
             # keep `depth` steps queued for the rows that still need tokens
@@ -642,9 +981,9 @@ class BatchSynthesizer:
                 drain(block=bool(pending) and not waiting)
                 announce()
                 if finished() and not pending and not closing and not waiting and \
-                        all(r.req is None for r in rows):
+                        not busy and not self._ctl and all(r.req is None for r in rows):
                     break
-                if not pending and not closing:
+                if not pending and not closing and not busy:
                     idle(now())
                 continue
             ev, entries = inflight.popleft()

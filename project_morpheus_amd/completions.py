@@ -55,7 +55,9 @@ def params_from_payload(p: Dict[str, Any]) -> Dict[str, Any]:
     them; ``repeat_last_n`` maps to ``penalty_last_n``: -1 the whole sequence (0), 0 the penalty
     off (``penalty`` 1.0), 1-255 the window.  ``code_grammar`` (true / false; anything else is
     an error) is returned as ``grammar`` when the payload names it: the stream then picks from
-    the Orpheus code grammar's allowed ids only."""
+    the Orpheus code grammar's allowed ids only.  ``prompt_prefix`` (a non-empty string; anything
+    else is an error) is returned as ``prefix``: the prompt continues that registered prefix; a
+    name the service does not know is the token source's ValueError (HTTP 400 as well)."""
     from .batching import check_params
 
     def whole(v, name):
@@ -84,6 +86,11 @@ def params_from_payload(p: Dict[str, Any]) -> Dict[str, Any]:
             if not isinstance(p["code_grammar"], bool):
                 raise ValueError(f"code_grammar must be true or false, got {p['code_grammar']!r}")
             out["grammar"] = p["code_grammar"]
+        if "prompt_prefix" in p:  # a registered prefix (cached voice prompt) the prompt continues
+            if not isinstance(p["prompt_prefix"], str) or not p["prompt_prefix"]:
+                raise ValueError("prompt_prefix must be the name of a registered prefix, got "
+                                 f"{p['prompt_prefix']!r}")
+            out["prefix"] = p["prompt_prefix"]
     except (TypeError, ValueError) as e:
         raise ValueError(f"bad generation parameter: {e}") from e
     check_params(out["penalty"], out["temperature"], out["top_p"], out["max_tokens"],

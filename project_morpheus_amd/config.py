@@ -206,6 +206,16 @@ def packed_prefill_default(environ=None) -> bool:
     return str(env.get("MORPHEUS_MX_PACKED_PREFILL", "")).strip().lower() in ("1", "true", "yes", "on")
 
 
+def prefix_slots_default(environ=None) -> int:
+    """Template KV slots a ``Service`` keeps for registered prefixes (cached voice prompts):
+    MORPHEUS_MX_PREFIX_SLOTS, 0 when unset or not a non-negative integer."""
+    env = os.environ if environ is None else environ
+    try:
+        return max(0, int(env.get("MORPHEUS_MX_PREFIX_SLOTS", "0")))
+    except (TypeError, ValueError):
+        return 0
+
+
 def request_seed(prompt_ids, seed=None) -> int:
     """The seed of one request: ``seed`` if given, else content-derived (CONTENT_SEED=1) or a
     fresh random 64-bit value."""

@@ -144,6 +144,14 @@ struct mx_llm {
   float* pk_h = nullptr;                  // [max_batch][hidden] the segments' last rows
   float* pk_logits = nullptr;             // [max_batch][vocab] their penalised logits
   std::vector<int32_t> pk_host;           // host copy of the table (one upload per call)
+  // prompt continuation (mx_llm_prefill_chunk / mx_llm_fork_slot): the id history of every slot's
+  // prompt lives in plain host memory, written at call time by every prefill entry point and
+  // copied by a fork; a final chunk uploads it once (DESIGN.md §3 "Prompt continuation")
+  std::vector<int32_t> slot_ids;          // [max_slots][max_pos] prompt ids the slot holds
+  std::vector<int> slot_len;              // ... and how many (tokens decoded behind them not counted)
+  std::vector<int> row_slot_h;            // per decode row: the KV slot it is bound to, -1 = parked
+  int32_t* cont_ids = nullptr;            // device [max_pos]: a final chunk's history upload
+                                          // (allocated by the first one, behind every other buffer)
   bool final = false;
   int max_rows = 0;
   int legacy_gemv = 0;          // option: grid-stride GEMV for R = 1 too (A/B timing)
@@ -259,6 +267,9 @@ extern "C" int mx_llm_create(int device, const mx_llm_config* cfg, mx_llm** out)
   x->row_chain.assign(c.max_batch, 0);
   x->row_origin.assign(c.max_batch, -1);
   x->slot_grammar.assign(c.max_slots, 0);
+  x->slot_ids.assign((size_t)c.max_slots * c.max_pos, 0);
+  x->slot_len.assign(c.max_slots, 0);
+  x->row_slot_h.assign(c.max_batch, -1);
   x->max_rows = c.max_batch > c.max_prefill ? c.max_batch : c.max_prefill;
   x->nsplit_max = c.max_pos / ATT_S_MIN;
   const int qkv_rows = c.heads * 128 + 2 * c.kv_heads * 128;
@@ -1030,6 +1041,19 @@ static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, in
   return e;
 }
 
+// Host mirror of a slot's prompt: ids [pos0, pos0 + n) recorded, the slot then holds pos0 + n.
+static void record_prompt(mx_llm* x, int slot, int pos0, const int32_t* ids, int n) {
+  std::memcpy(x->slot_ids.data() + (size_t)slot * x->c.max_pos + pos0, ids, (size_t)n * 4);
+  x->slot_len[slot] = pos0 + n;
+}
+
+// The active decode row bound to `slot`, or -1.
+static int row_of_slot(const mx_llm* x, int slot) {
+  for (int r = 0; r < x->c.max_batch; ++r)
+    if (x->row_active[r] && x->row_slot_h[r] == slot) return r;
+  return -1;
+}
+
 extern "C" int mx_llm_prefill(mx_llm* x, int slot, int row, const int32_t* ids, int n,
                               const mx_sampling* sp, void* stream) {
   return mx_llm_prefill_ex(x, slot, row, ids, n, sp, nullptr, stream);
@@ -1102,6 +1126,8 @@ extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* id
   x->row_samples[row] = samples ? 1 : 0;
   x->row_chain[row] = chain ? 1 : 0;
   x->row_origin[row] = origin;
+  record_prompt(x, slot, 0, ids, n);
+  x->row_slot_h[row] = slot;
   return MX_OK;
 }
 
@@ -1227,7 +1253,154 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
     x->row_samples[g.row] = samples ? 1 : 0;
     x->row_chain[g.row] = samples && (g.ext.top_k > 0 || g.ext.min_p > 0.f) ? 1 : 0;
     x->row_origin[g.row] = hs[s].origin;
+    record_prompt(x, g.slot, 0, g.ids_host, g.n_ids);
+    x->row_slot_h[g.row] = g.slot;
   }
+  return MX_OK;
+}
+
+// Prompt continuation: a chunk of a prompt behind the pos0 positions its slot already holds.
+// The rows carry pos = pos0 + i; the attention grid is sized by max_len = pos0 + n (prompt rows
+// attending over more positions than there are rows: the multi-row kernel with the split counts
+// decode rows reach, the one-row kernels for a one-id chunk).  A non-final chunk runs the layers
+// and appends K / V, nothing else.  The final chunk builds the slot's penalty state from the id
+// history over [0, pos0 + n) (the host mirror, uploaded once), sets the grammar origin to
+// pos0 + n and runs head, sampler and commit on its last row as mx_llm_prefill_ex does for n.
+// pos0 = 0 with last = 1 IS mx_llm_prefill_ex (the same launches).
+extern "C" int mx_llm_prefill_chunk(mx_llm* x, const mx_prefill_chunk* ck, void* stream) {
+  if (!x || !ck) return MX_ERR_ARG;
+  if (!ck->ids_host) MX_FAIL(x, MX_ERR_ARG, "chunk without ids");
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  const auto& c = x->c;
+  const int slot = ck->slot, row = ck->row, n = ck->n_ids, pos0 = ck->pos0;
+  const bool last = ck->last != 0;
+  const int32_t* ids = ck->ids_host;
+  // every refusal first: a refused call enqueues nothing and changes no host state
+  if (slot < 0 || slot >= c.max_slots || (last && (row < 0 || row >= c.max_batch)))
+    MX_FAIL(x, MX_ERR_ARG, "slot/row out of range");
+  if (n < 1 || n > c.max_prefill) MX_FAIL(x, MX_ERR_ARG, "bad chunk length");
+  if (pos0 < 0 || (long long)pos0 + n >= c.max_pos)
+    MX_FAIL(x, MX_ERR_ARG, "chunk does not fit max_pos");
+  for (int i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= c.vocab) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
+  const mx_sampling& sp = ck->params;
+  const mx_sampling_ext& xe = ck->ext;
+  if (last) {
+    if (!(sp.repetition_penalty > 0.f) || !(sp.top_p > 0.f) || sp.temperature < 0.f)
+      MX_FAIL(x, MX_ERR_ARG, "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0");
+    if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
+        xe.penalty_last_n >= PEN_RING)
+      MX_FAIL(x, MX_ERR_ARG,
+              "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255");
+  }
+  if (pos0 == 0 && last)
+    return mx_llm_prefill_ex(x, slot, row, ids, n, &sp, &xe, stream);
+  // (pos0 = 0 starts the slot over, as every prefill does)
+  if (pos0 != 0 && pos0 != x->slot_len[slot])
+    MX_FAIL(x, MX_ERR_STATE, "chunk at position " + std::to_string(pos0) + ": the slot holds " +
+                                 std::to_string(x->slot_len[slot]));
+  if (row_of_slot(x, slot) >= 0)
+    MX_FAIL(x, MX_ERR_STATE, "chunk onto a slot bound to an active row");
+  const int max_len = pos0 + n;
+  RowSet rs{x->h_pre, x->pre_slot, x->pre_pos, n, max_len, att_cpw_auto(x, n, max_len),
+            att_nw_of(x, n, max_len), 0, false};
+  const int S = 32 * rs.nw * rs.cpw;
+  rs.nsplit = (max_len + S - 1) / S;
+  // the launch's own argument checks (launch_attention), made before anything is enqueued: the
+  // split count one launch may merge, and the partial slots a (row, kv head) has
+  const int stride = S < ATT_S_MIN ? c.max_pos / 64 : c.max_pos / ATT_S_MIN;
+  if (rs.nsplit > ATT_MAX_SPLITS || (c.max_pos + S - 1) / S > stride)
+    MX_FAIL(x, MX_ERR_ARG, "chunk: the context needs more attention splits than one launch merges");
+  hipStream_t st = (hipStream_t)stream;
+  MX_TRY(x, hipSetDevice(x->device));
+  const int32_t* dev_ids = x->pre_ids;
+  if (last) {
+    // the slot's history [0, pos0) and the chunk's ids behind it, one contiguous device copy
+    if (!x->cont_ids) MX_TRY(x, x->alloc(&x->cont_ids, (size_t)c.max_pos));
+    MX_TRY(x, launch_set_slot_params(x->penalty, x->samp_temp, x->samp_top_p, x->samp_seed, slot,
+                                     sp.repetition_penalty, sp.temperature,
+                                     sp.top_p < 1.f ? sp.top_p : 1.f, sp.seed, st));
+    MX_TRY(x, hipMemsetAsync(x->seen + (size_t)slot * c.vocab, 0, c.vocab, st));
+    MX_TRY(x, hipMemcpyAsync(x->cont_ids, x->slot_ids.data() + (size_t)slot * c.max_pos,
+                             (size_t)pos0 * 4, hipMemcpyHostToDevice, st));
+    MX_TRY(x, hipMemcpyAsync(x->cont_ids + pos0, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    dev_ids = x->cont_ids + pos0;
+  } else {
+    MX_TRY(x, hipMemcpyAsync(x->pre_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  }
+  MX_TRY(x, launch_set_rows(x->pre_slot, x->pre_pos, n, slot, pos0, st));
+  // (no seen marks here: the final chunk marks the whole history behind the layers)
+  MX_TRY(x, launch_embed_rows(dev_ids, n, slot, x->embed, c.hidden, c.vocab, nullptr, x->h_pre, st));
+  MX_TRY(x, enqueue_layers(x, rs, st, nullptr));
+  if (!last) {
+    record_prompt(x, slot, pos0, ids, n);
+    return MX_OK;
+  }
+  const int win = xe.penalty_last_n;
+  MX_TRY(x, launch_set_slot_ext(x->samp_top_k, x->samp_min_p, x->last_n, slot, xe.top_k,
+                                xe.min_p, win, st));
+  MX_TRY(x, hipMemsetAsync(x->recent + (size_t)slot * PEN_RING, 0, PEN_RING * 4, st));
+  if (win > 0)  // the last N positions of the whole prompt: they may straddle the seam
+    MX_TRY(x, launch_window_prefill(x->cont_ids, max_len, win, slot, c.vocab, x->seen, x->recent, st));
+  else
+    MX_TRY(x, launch_mark_seen(x->cont_ids, max_len, slot, c.vocab, x->seen, st));
+  const int origin = x->gram_on && x->slot_grammar[slot] ? max_len : -1;
+  if (x->gram_on) MX_TRY(x, launch_set_slot_origin(x->gram_origin, slot, origin, st));
+  MX_TRY(x, hipMemsetAsync(x->best + row, 0, 8, st));
+  const bool samples = sp.temperature > 0.f;
+  const bool chain = samples && (xe.top_k > 0 || xe.min_p > 0.f);
+  MX_TRY(x, enqueue_head(x, x->h_pre + (size_t)(n - 1) * c.hidden, x->pre_slot + (n - 1),
+                         x->pre_pos + (n - 1), 1, x->best + row,
+                         chain ? SMP_CHAIN : samples ? SMP_PLAIN : SMP_NONE,
+                         origin >= 0 && x->grammar_head && x->win_n > 0, st));
+  // bind decode row -> slot at the prompt's last position, then commit (advances to pos0 + n)
+  MX_TRY(x, launch_set_rows(x->row_slot + row, x->row_pos + row, 1, slot, max_len - 1, st));
+  CommitArgs cm{};
+  cm.best = x->best + row; cm.row_slot = x->row_slot + row; cm.row_pos = x->row_pos + row;
+  cm.row_token = x->row_token + row; cm.seen = x->seen; cm.hist = x->hist_dev;
+  cm.embed = x->embed; cm.h = x->h_dec + (size_t)row * c.hidden; cm.hidden = c.hidden;
+  cm.vocab = c.vocab; cm.max_pos = c.max_pos; cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
+  cm.last_n = x->last_n; cm.recent = x->recent;
+  MX_TRY(x, launch_commit(cm, 1, st));
+  x->pos_mirror[row] = max_len;
+  x->row_active[row] = 1;
+  x->row_samples[row] = samples ? 1 : 0;
+  x->row_chain[row] = chain ? 1 : 0;
+  x->row_origin[row] = origin;
+  record_prompt(x, slot, pos0, ids, n);
+  x->row_slot_h[row] = slot;
+  return MX_OK;
+}
+
+// dst holds src's first n_pos positions afterwards: K / V of every layer (one kv_fork_kernel
+// launch, ordered on the stream) and the id history (host mirror).  No penalty state: the
+// request's final chunk builds that for its own parameters.
+extern "C" int mx_llm_fork_slot(mx_llm* x, int dst, int src, int n_pos, void* stream) {
+  if (!x) return MX_ERR_ARG;
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  const auto& c = x->c;
+  if (dst < 0 || dst >= c.max_slots || src < 0 || src >= c.max_slots)
+    MX_FAIL(x, MX_ERR_STATE, "fork: slot out of range");
+  if (dst == src) MX_FAIL(x, MX_ERR_STATE, "fork: dst is src");
+  if (n_pos < 1 || n_pos > x->slot_len[src])
+    MX_FAIL(x, MX_ERR_STATE, "fork of " + std::to_string(n_pos) + " positions: the source holds " +
+                                 std::to_string(x->slot_len[src]));
+  if (row_of_slot(x, dst) >= 0) MX_FAIL(x, MX_ERR_STATE, "fork: dst is bound to an active row");
+  MX_TRY(x, hipSetDevice(x->device));
+  KvForkArgs a{};
+  a.kcache = x->kcache; a.vcache = x->vcache; a.kv_layer_elems = x->kv_layer_elems;
+  a.layers = c.layers; a.kv_heads = c.kv_heads; a.max_pos = c.max_pos;
+  a.src = src; a.dst = dst; a.chunks = (n_pos + 31) / 32; a.runs = 2 * c.layers * c.kv_heads;
+  MX_TRY(x, launch_kv_fork(a, x->cus, (hipStream_t)stream));
+  std::memcpy(x->slot_ids.data() + (size_t)dst * c.max_pos,
+              x->slot_ids.data() + (size_t)src * c.max_pos, (size_t)n_pos * 4);
+  x->slot_len[dst] = n_pos;
+  return MX_OK;
+}
+
+extern "C" int mx_llm_slot_len(const mx_llm* x, int slot, int* n_pos) {
+  if (!x || !n_pos || slot < 0 || slot >= x->c.max_slots) return MX_ERR_ARG;
+  *n_pos = x->slot_len[slot];
   return MX_OK;
 }
 
@@ -1885,6 +2058,7 @@ extern "C" int mx_llm_release_row(mx_llm* x, int row, void* stream) {
   x->row_samples[row] = 0;
   x->row_chain[row] = 0;
   x->row_origin[row] = -1;
+  x->row_slot_h[row] = -1;
   return MX_OK;
 }
 
@@ -1901,6 +2075,8 @@ extern "C" int mx_llm_move_row(mx_llm* x, int dst, int src, void* stream) {
   x->row_chain[dst] = x->row_chain[src];
   x->row_origin[dst] = x->row_origin[src];
   x->row_origin[src] = -1;
+  x->row_slot_h[dst] = x->row_slot_h[src];
+  x->row_slot_h[src] = -1;
   x->pos_mirror[src] = 0;
   x->row_active[src] = 0;
   x->row_samples[src] = 0;

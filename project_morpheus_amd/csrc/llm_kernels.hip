@@ -1478,6 +1478,71 @@ hipError_t launch_frag_major(const void* src, void* dst, int N, int K, int esz, 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------
+// Prompt continuation (mx_llm_prefill_chunk / mx_llm_fork_slot): the KV fork and the
+// final chunk's penalty state from the slot's id history.
+// ---------------------------------------------------------------------------------
+// KV fork: K and V of a (layer, slot, kv head) are one block of 32-position chunks (8 KB, 512
+// 16-byte units) in position order, so a slot's first `chunks` chunks are one contiguous run
+// per block.  One launch copies that run of every block -- run = (K | V, layer, kv head) --
+// from `src` to `dst`.  A block takes chunk pairs grid-stride; every lane issues its four
+// 16-byte loads (two per chunk) before the first store.
+__global__ __launch_bounds__(256) void kv_fork_kernel(KvForkArgs a) {
+  const long long total = (long long)a.runs * a.chunks;
+  const int per_kind = a.layers * a.kv_heads;
+  for (long long u = 2ll * blockIdx.x; u < total; u += 2ll * gridDim.x) {
+    const uint4* s[2];
+    uint4* d[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const long long uj = u + j < total ? u + j : u;  // (odd total: the last pair repeats)
+      const int run = (int)(uj / a.chunks), ch = (int)(uj % a.chunks);
+      const int kind = run / per_kind, rem = run % per_kind;
+      const int layer = rem / a.kv_heads, kvh = rem % a.kv_heads;
+      uint16_t* base = (kind ? a.vcache : a.kcache) + a.kv_layer_elems * layer;
+      const size_t chunk_off = (size_t)ch * 4096;
+      s[j] = reinterpret_cast<const uint4*>(
+          base + ((size_t)a.src * a.kv_heads + kvh) * a.max_pos * 128 + chunk_off);
+      d[j] = reinterpret_cast<uint4*>(
+          base + ((size_t)a.dst * a.kv_heads + kvh) * a.max_pos * 128 + chunk_off);
+    }
+    const uint4 v0 = s[0][threadIdx.x], v1 = s[0][threadIdx.x + 256];
+    const uint4 v2 = s[1][threadIdx.x], v3 = s[1][threadIdx.x + 256];
+    d[0][threadIdx.x] = v0;
+    d[0][threadIdx.x + 256] = v1;
+    if (u + 1 < total) {
+      d[1][threadIdx.x] = v2;
+      d[1][threadIdx.x + 256] = v3;
+    }
+  }
+}
+
+hipError_t launch_kv_fork(const KvForkArgs& a, int cus, hipStream_t st) {
+  if (a.chunks < 1 || a.chunks > a.max_pos / 32 || a.runs < 1 || a.src == a.dst)
+    return hipErrorInvalidValue;
+  // grid from the CU count: eight 256-lane blocks per CU hold 64 B per lane in flight, and no
+  // more blocks than there are chunk pairs
+  const long long pairs = ((long long)a.runs * a.chunks + 1) / 2;
+  const int grid = (int)std::min<long long>(pairs, (long long)std::max(cus, 1) * 8);
+  hipLaunchKernelGGL(kv_fork_kernel, dim3(grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// Whole-sequence penalty state of a final chunk: seen[slot][ids[i]] = 1 for the n ids of the
+// slot's history (same-value byte stores from many lanes, as embed_rows_kernel's marks).
+__global__ __launch_bounds__(256) void mark_seen_kernel(const int32_t* ids, int n, int slot,
+                                                        int vocab, uint8_t* seen) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) seen[(size_t)slot * vocab + ids[i]] = 1;
+}
+
+hipError_t launch_mark_seen(const int32_t* ids, int n, int slot, int vocab, uint8_t* seen,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(mark_seen_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ids, n, slot,
+                     vocab, seen);
+  return hipGetLastError();
+}
+
 hipError_t launch_to_f32(float* dst, const void* src, int64_t n, int src_bf16, hipStream_t st) {
   const int64_t blocks = (n + 255) / 256;
   hipLaunchKernelGGL(to_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dst, src, n, src_bf16);

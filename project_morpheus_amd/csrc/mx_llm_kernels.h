@@ -281,6 +281,23 @@ hipError_t launch_pack_tail(const PackTailArgs& a, int n_segs, hipStream_t st);
 // dst[rows[k]][0, V) = src[k][0, V): the kept logits to the decode rows' own lines
 hipError_t launch_pack_logits(float* dst, const float* src, const int32_t* rows, int n_segs,
                               int V, hipStream_t st);
+// ---- prompt continuation (mx_llm_prefill_chunk / mx_llm_fork_slot) --------------------
+struct KvForkArgs {
+  uint16_t* kcache;        // all layers: [layers][slots][kv_heads][max_pos * 128]
+  uint16_t* vcache;
+  size_t kv_layer_elems;   // elements of one layer
+  int layers, kv_heads, max_pos;
+  int src, dst;            // KV slots
+  int chunks;              // 32-position chunks copied per block: ceil(n_pos / 32)
+  int runs;                // 2 * layers * kv_heads
+};
+// dst's first `chunks` chunks of every (K | V, layer, kv head) block = src's (one launch; the
+// grid is sized from `cus`).  hipErrorInvalidValue on chunks outside [1, max_pos / 32] or
+// src == dst.
+hipError_t launch_kv_fork(const KvForkArgs& a, int cus, hipStream_t st);
+// seen[slot][ids[i]] = 1, i < n (the whole-sequence penalty state from an id history)
+hipError_t launch_mark_seen(const int32_t* ids, int n, int slot, int vocab, uint8_t* seen,
+                            hipStream_t st);
 hipError_t launch_to_f32(float* dst, const void* src, int64_t n, int src_bf16, hipStream_t st);
 // [N][K] (esz bytes per element) -> fragment-major copy for the multi-row GEMM (mx_rows_v4.inc)
 hipError_t launch_frag_major(const void* src, void* dst, int N, int K, int esz, hipStream_t st);

@@ -77,6 +77,19 @@ def _worker(device: int, inbox, outbox, factory: Callable, content_seed: int = 0
             with lock:
                 handles[rid] = h
             threading.Thread(target=pump, args=(rid, h), daemon=True).start()
+        elif kind == "register_prefix":
+            # (ahead of every later submit in this inbox: the service sees the name at once)
+            _, name, ids = msg
+            try:
+                err = None
+                if ids is None:
+                    svc.unregister_prefix(name)
+                else:  # (what the service refuses at once; its loop reports the rest per request)
+                    err = getattr(svc.register_prefix(name, ids), "error", None)
+            except BaseException as e:
+                err = e
+            if err is not None:
+                outbox.put(("prefix", -1, (device, name, repr(err))))
         elif kind == "cancel":
             with lock:
                 h = handles.get(msg[1])
@@ -142,6 +155,8 @@ class GpuPool:
         self._handles: Dict[int, PoolHandle] = {}
         self._lock = threading.Lock()
         self._ids = itertools.count()
+        self.prefixes: Dict[str, List[int]] = {}   # registered prefixes: replayed to a respawn
+        self.prefix_errors: List[tuple] = []       # (device, name, error) a worker reported
         ready = 0
         while ready < len(self.devices):
             kind, _, info = self.outbox.get(timeout=start_timeout)
@@ -171,6 +186,9 @@ class GpuPool:
                 return
             if kind == "closed":
                 return
+            if kind == "prefix":
+                self.prefix_errors.append(payload)
+                continue
             if kind in ("ready", "dead"):  # a replacement worker came up (or failed to)
                 w = self.devices.index(payload[0])
                 with self._lock:
@@ -215,6 +233,11 @@ class GpuPool:
         self.procs[w] = ctx.Process(target=_worker, args=(self.devices[w], self.inboxes[w],
                                                           self.outbox, self.factory,
                                                           _content_seed()), daemon=True)
+        # the registry first: the new worker registers every prefix before it takes a request
+        with self._lock:
+            known = list(self.prefixes.items())
+        for name, ids in known:
+            self.inboxes[w].put(("register_prefix", name, ids))
         self.procs[w].start()
         self._respawned[w] = True
 
@@ -224,6 +247,39 @@ class GpuPool:
         if not live:
             raise RuntimeError("no GPU worker is alive")
         return min(live, key=lambda i: (self.load[i], i))
+
+    def register_prefix(self, name: str, ids) -> List[int]:
+        """Register ``ids`` under ``name`` on EVERY worker (a request naming it may land on any
+        GPU) and keep it for workers respawned later.  -> the workers it was sent to; a worker
+        that refuses it reports into ``prefix_errors``."""
+        from .batching import check_prefix
+        check_prefix(name)
+        if name is None:
+            raise ValueError("prefix name must be a non-empty string")
+        ids = [int(t) for t in ids]
+        if not ids:
+            raise ValueError("a prefix needs ids")
+        with self._lock:
+            self.prefixes[name] = ids
+            sent = [w for w in range(len(self.devices)) if self.alive[w]]
+            for w in sent:
+                self.inboxes[w].put(("register_prefix", name, ids))
+        return sent
+
+    def unregister_prefix(self, name: str) -> None:
+        with self._lock:
+            if self.prefixes.pop(name, None) is None:
+                raise KeyError(f"unknown prefix {name!r}")
+            for w in range(len(self.devices)):
+                if self.alive[w]:
+                    self.inboxes[w].put(("register_prefix", name, None))
+
+    def _known_prefix(self, kw) -> None:
+        from .batching import UnknownPrefix, check_prefix
+        prefix = kw.get("prefix")
+        check_prefix(prefix)
+        if prefix is not None and prefix not in self.prefixes:
+            raise UnknownPrefix(f"unknown prefix {prefix!r}")
 
     def _enqueue(self, cost: int, make_msg) -> PoolHandle:
         with self._lock:
@@ -238,12 +294,14 @@ class GpuPool:
     def submit(self, text: str, voice: str = I.DEFAULT_VOICE, max_tokens: Optional[int] = None,
                **kw) -> PoolHandle:
         kw = dict(kw, max_tokens=max_tokens)
+        self._known_prefix(kw)
         return self._enqueue(max_tokens or I.MAX_TOKENS,
                              lambda rid: ("submit", rid, text, voice, kw))
 
     def submit_tokens(self, prompt_ids, max_tokens: Optional[int] = None, **kw) -> PoolHandle:
         """Token-only stream on the least-loaded GPU (/v1/completions): ``get`` -> id | None."""
         kw = dict(kw, max_tokens=max_tokens)
+        self._known_prefix(kw)
         ids = [int(t) for t in prompt_ids]
         return self._enqueue(max_tokens or I.MAX_TOKENS,
                              lambda rid: ("submit_tokens", rid, ids, kw))

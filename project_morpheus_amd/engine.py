@@ -148,6 +148,47 @@ class LlmEngine:
         self._check(self.lib.mx_llm_prefill_batch(self.h, arr, len(segs),
                                                   C.c_void_p(stream.cuda_stream)))
 
+    def prefill_chunk(self, slot: int, ids: Sequence[int], pos0: int, stream, *,
+                      last: bool = False, row: Optional[int] = None, penalty: float = 1.1,
+                      temperature: float = 0.0, top_p: float = 1.0, seed: int = 0,
+                      top_k: int = 0, min_p: float = 0.0, penalty_last_n: int = 0,
+                      grammar: bool = False) -> None:
+        """One chunk of a prompt behind the ``pos0`` positions ``slot`` already holds
+        (mx_llm_prefill_chunk).  ``last=False``: the layers and the KV append only; no row, no
+        generation parameters.  ``last=True`` ends the prompt: needs ``row`` and takes
+        ``prefill``'s generation parameters; the stream then continues as after one ``prefill`` of
+        all the chunks' ids.  A call the device refuses changes nothing."""
+        if last:
+            if row is None:
+                raise ValueError("the final chunk needs a decode row")
+            if bool(grammar) != self._slot_grammar.get(slot, False) and 0 <= slot < self.max_slots:
+                self._check(self.lib.mx_llm_set_slot_grammar(self.h, slot, int(bool(grammar))))
+                self._slot_grammar[slot] = bool(grammar)
+        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        ck = _lib.PrefillChunk(slot=int(slot), row=int(row) if last else 0,
+                               ids_host=arr.ctypes.data, n_ids=len(arr), pos0=int(pos0),
+                               last=int(bool(last)))
+        if last:
+            ck.params = _lib.Sampling(temperature=float(temperature), top_p=float(top_p),
+                                      repetition_penalty=float(penalty),
+                                      seed=int(seed) & (2**64 - 1))
+            ck.ext = _lib.SamplingExt(top_k=int(top_k), min_p=float(min_p),
+                                      penalty_last_n=int(penalty_last_n))
+        self._check(self.lib.mx_llm_prefill_chunk(self.h, C.byref(ck),
+                                                  C.c_void_p(stream.cuda_stream)))
+
+    def fork_slot(self, dst: int, src: int, n_pos: int, stream) -> None:
+        """KV slot ``dst`` holds ``src``'s first ``n_pos`` positions afterwards (K / V of every
+        layer and the id history; one device copy ordered on ``stream``)."""
+        self._check(self.lib.mx_llm_fork_slot(self.h, int(dst), int(src), int(n_pos),
+                                              C.c_void_p(stream.cuda_stream)))
+
+    def slot_len(self, slot: int) -> int:
+        """Prompt positions ``slot`` holds (the library's host mirror)."""
+        n = C.c_int(0)
+        self._check(self.lib.mx_llm_slot_len(self.h, int(slot), C.byref(n)))
+        return n.value
+
     def decode(self, n_rows: int, stream) -> None:
         """One step for rows [0, n_rows), each under its slot's generation parameters."""
         self._check(self.lib.mx_llm_decode(self.h, n_rows, C.c_void_p(stream.cuda_stream)))

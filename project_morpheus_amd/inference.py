@@ -89,6 +89,25 @@ def prompt_ids(text_ids: Sequence[int]) -> List[int]:
     return [START_TOKEN_ID] + list(text_ids) + list(END_TOKEN_IDS)
 
 
+END_OF_SPEECH_ID, END_OF_AI_ID = 128258, 128262
+
+
+def frame_voice_pairs(pairs: Iterable) -> List[int]:
+    """Id framing of zero-shot voice-cloning context: every (text ids, audio ids) pair as
+    ``[128259] text [128009, 128260, 128261, 128257] audio [128258, 128262]``, pair after pair;
+    the new text's ``prompt_ids`` goes behind it (as the suffix of a registered prefix).  The
+    prompt part is ``prompt_ids``' framing (engine_class.py:87-95); the closing pair of ids
+    (end of speech, end of AI) is NOT pinned by the reference tree (unpinned).
+    The engine-level API takes raw ids, so a caller may frame differently."""
+    out: List[int] = []
+    for text_ids, audio_ids in pairs:
+        text_ids, audio_ids = [int(t) for t in text_ids], [int(t) for t in audio_ids]
+        if not text_ids or not audio_ids:
+            raise ValueError("a voice pair needs text ids and audio ids")
+        out += prompt_ids(text_ids) + audio_ids + [END_OF_SPEECH_ID, END_OF_AI_ID]
+    return out
+
+
 def split_text_into_sentences(text: str) -> List[str]:
     """Sentence split: a whitespace char after . ! ? ends a sentence unless the char two
     back is '.' or ' ' (abbreviation heuristic); pieces < 20 chars merge forward."""

@@ -24,7 +24,8 @@ import torch
 
 from . import config as C
 from . import inference as I
-from .batching import BatchSynthesizer, StreamHandle, StreamRequest
+from .batching import (BatchSynthesizer, StreamHandle, StreamRequest, UnknownPrefix,
+                       check_prefix)
 from .engine import LlmEngine, SnacDecoder
 from .tokenizer import Tokenizer, default_tokenizer
 from .weights import (load_hf_llm, load_snac_state_dict, synthetic_llm_weights,
@@ -36,8 +37,10 @@ class Service:
                  llm_weights=None, snac_weights=None, max_pos: int = 2048,
                  tokenizer: Optional[Tokenizer] = None, max_prefill: int = 512,
                  max_batch: int = C.MX_MAX_SLOTS, synthetic_audio: Optional[bool] = None,
-                 packed_prefill: Optional[bool] = None):
-        """``synthetic_audio``: feed the SNAC schedule a seeded audio-code stream per request
+                 packed_prefill: Optional[bool] = None, prefix_slots: Optional[int] = None):
+        """``prefix_slots``: template KV slots for registered prefixes (``register_prefix``;
+        None: MORPHEUS_MX_PREFIX_SLOTS, 0 when unset -- nothing is allocated for them then).
+        ``synthetic_audio``: feed the SNAC schedule a seeded audio-code stream per request
         (default: whenever the LLM weights are synthetic, which never speak).
         ``packed_prefill``: admit the requests of one loop iteration through packed prefills
         (None: MORPHEUS_MX_PACKED_PREFILL, off when unset)."""
@@ -57,11 +60,13 @@ class Service:
                 synthetic_snac_weights()
         self.cfg, self.device = cfg, device
         self.synthetic_audio = synthetic if synthetic_audio is None else synthetic_audio
-        self.llm = LlmEngine(cfg, llm_weights, device=device, max_slots=max_batch,
+        prefix_slots = C.prefix_slots_default() if prefix_slots is None else int(prefix_slots)
+        self.llm = LlmEngine(cfg, llm_weights, device=device, max_slots=max_batch + prefix_slots,
                              max_pos=max_pos, max_batch=max_batch, max_prefill=max_prefill)
         del llm_weights
         self.snac = SnacDecoder(snac_weights, device=device, max_batch=max_batch)
-        self.batch = BatchSynthesizer(self.llm, self.snac, packed_prefill=packed_prefill).start()
+        self.batch = BatchSynthesizer(self.llm, self.snac, packed_prefill=packed_prefill,
+                                      prefix_slots=prefix_slots).start()
         self.tok = tokenizer or default_tokenizer()
 
     @classmethod
@@ -84,14 +89,32 @@ class Service:
     def prompt_ids(self, text: str, voice: str):
         return I.prompt_ids(self.tok.encode(f"{I.resolve_voice(voice)}: {text}"))
 
+    def register_prefix(self, name: str, ids):
+        """Prefill ``ids`` (raw ids, e.g. ``inference.frame_voice_pairs``) once under ``name``;
+        requests submitted with ``prefix=name`` continue behind them.  -> a handle
+        (``result()`` waits and raises what refused it)."""
+        return self.batch.register_prefix(name, ids)
+
+    def unregister_prefix(self, name: str):
+        return self.batch.unregister_prefix(name)
+
+    def _check_prefix(self, prefix) -> None:
+        """Refused at submit time (ValueError: HTTP 400): a prefix that is no name, or that
+        nobody registered here.  (One evicted later fails its request alone, in the loop.)"""
+        check_prefix(prefix)
+        if prefix is not None and not self.batch.has_prefix(prefix):
+            raise UnknownPrefix(f"unknown prefix {prefix!r}")
+
     def submit(self, text: str, voice: str = I.DEFAULT_VOICE, max_tokens: Optional[int] = None,
                penalty: float = I.REPETITION_PENALTY, temperature: Optional[float] = None,
                top_p: Optional[float] = None, seed: Optional[int] = None,
                prompt_ids=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                penalty_last_n: Optional[int] = None,
-               grammar: Optional[bool] = None) -> StreamHandle:
+               grammar: Optional[bool] = None, prefix: Optional[str] = None) -> StreamHandle:
         """Queue one utterance on this GPU's batch loop (non-blocking).  ``grammar``: decode
-        under the Orpheus code grammar (None: MORPHEUS_MX_GRAMMAR, off when unset)."""
+        under the Orpheus code grammar (None: MORPHEUS_MX_GRAMMAR, off when unset).
+        ``prefix``: a registered prefix the prompt continues (``register_prefix``)."""
+        self._check_prefix(prefix)
         ids = list(prompt_ids) if prompt_ids is not None else self.prompt_ids(text, voice)
         max_tokens = max_tokens or I.MAX_TOKENS
         # one utterance's random streams (sampling, SNAC noise, synthetic codes) come from ONE
@@ -105,7 +128,7 @@ class Service:
             top_k=I.TOP_K if top_k is None else top_k,
             min_p=I.MIN_P if min_p is None else min_p,
             penalty_last_n=I.REPEAT_LAST_N if penalty_last_n is None else penalty_last_n,
-            grammar=C.grammar_default() if grammar is None else bool(grammar),
+            grammar=C.grammar_default() if grammar is None else bool(grammar), prefix=prefix,
             inject_ids=C.synthetic_audio_ids(max_tokens, seed=key)
             if self.synthetic_audio else None)
         if self.synthetic_audio:
@@ -116,8 +139,10 @@ class Service:
                       temperature: Optional[float] = None, top_p: Optional[float] = None,
                       penalty: float = I.REPETITION_PENALTY, seed: Optional[int] = None,
                       top_k: Optional[int] = None, min_p: Optional[float] = None,
-                      penalty_last_n: Optional[int] = None, grammar: Optional[bool] = None):
+                      penalty_last_n: Optional[int] = None, grammar: Optional[bool] = None,
+                      prefix: Optional[str] = None):
         """Token-only stream (completions surface): a TokenHandle of generated ids."""
+        self._check_prefix(prefix)
         ids = list(prompt_ids)
         key = C.request_seed(ids, seed)
         req = StreamRequest(prompt_ids=ids, max_tokens=max_tokens or I.MAX_TOKENS,
@@ -128,7 +153,8 @@ class Service:
                             min_p=I.MIN_P if min_p is None else min_p,
                             penalty_last_n=I.REPEAT_LAST_N if penalty_last_n is None
                             else penalty_last_n,
-                            grammar=C.grammar_default() if grammar is None else bool(grammar))
+                            grammar=C.grammar_default() if grammar is None else bool(grammar),
+                            prefix=prefix)
         return self.batch.submit(req)
 
     def stream(self, text: str, voice: str = I.DEFAULT_VOICE, max_tokens: Optional[int] = None,
