@@ -9,6 +9,8 @@
  *                (SamplingParams engine_class.py:106-112), llama.cpp Llama(...)/text_to_speech
  *                Morpheus_Client/tts_engine/llama_local.py:42-52,77, and the remote
  *                /v1/completions stream Morpheus_Client/tts_engine/remote_backend.py:64-117.
+ *   mx_snac_enc_*  replaces snac.SNAC.encode(audio) (third-party snac 1.2.x): reference audio
+ *                -> the speech codes of a voice prompt.
  *   mx_snac_*  replaces snac.SNAC.decode(codes) + slice + PCM16 in convert_to_audio
  *                Morpheus_Client/tts_engine/speechpipe.py:76-129 (model load :41-49).
  *
@@ -44,6 +46,7 @@ extern "C" {
 
 typedef struct mx_llm mx_llm;
 typedef struct mx_snac mx_snac;
+typedef struct mx_snac_enc mx_snac_enc;
 
 /* Llama-3 decoder shape (Orpheus-3B: 3072/28/24/8/128/8192/156940), limits and eps. */
 typedef struct mx_llm_config {
@@ -335,6 +338,35 @@ int mx_snac_decode(mx_snac* ctx, const int32_t* frames, int n_frames, int batch,
                    float* audio, int lo, int hi, void* stream);
 const char* mx_snac_last_error(const mx_snac* ctx);
 void mx_snac_destroy(mx_snac* ctx);
+
+/* ---- SNAC 24 kHz encoder + residual vector quantiser (replaces SNAC.encode) ---------- */
+/* A context of its own (nothing is shared with mx_snac).  Buffers are sized by max_frames
+ * (1 .. 4096) at finalize: 3 x 393,216 bytes per frame. */
+int mx_snac_enc_create(int device, int max_frames, mx_snac_enc** out);
+/* names: enc.in.{w,b} [48*7], enc.b{k}.r{j}.{alpha1,dw.w,dw.b,alpha2,pw.w,pw.b},
+ * enc.b{k}.alpha, enc.b{k}.down.{w,b} ([2C][C][2s], C = 48 << k, s = 2, 4, 8, 8),
+ * enc.out.dw.{w,b} [768*7], q{i}.in_proj.{w,b} ([8][768]), q{i}.codebook [4096*8],
+ * q{i}.out_proj.{w,b} (weight norm already folded; layouts as torch Conv1d weights).
+ * MX_ERR_STATE after finalize. */
+int mx_snac_enc_set_weight(mx_snac_enc* ctx, const char* name, const void* dev_data,
+                           int64_t numel, int dtype);
+int mx_snac_enc_finalize(mx_snac_enc* ctx);
+/* audio: device-accessible fp32 mono 24 kHz [n_samples], read as zeros past its end up to the
+ * next multiple of 2048; frames_out: device-accessible int32 [7 * ceil(n_samples / 2048)] in
+ * speechpipe order (frame f = c0[f], c1[2f], c2[4f], c2[4f+1], c1[2f+1], c2[4f+2], c2[4f+3]).
+ * Enqueued on `stream`; deterministic (no atomics).  Every check runs before anything is
+ * enqueued: MX_ERR_ARG on a null pointer, n_samples < 1 or more than max_frames frames,
+ * MX_ERR_STATE before finalize. */
+int mx_snac_enc_encode(mx_snac_enc* ctx, const float* audio, int64_t n_samples,
+                       int32_t* frames_out, void* stream);
+/* parity/debug: the latent z, channels-last [4 * n_frames][768] */
+int mx_snac_enc_latent(mx_snac_enc* ctx, const float* audio, int64_t n_samples, float* z_out,
+                       void* stream);
+/* parity/debug: the quantiser alone on a caller's z [4 * n_frames][768] */
+int mx_snac_enc_quantize(mx_snac_enc* ctx, const float* z, int n_frames, int32_t* frames_out,
+                         void* stream);
+const char* mx_snac_enc_last_error(const mx_snac_enc* ctx);
+void mx_snac_enc_destroy(mx_snac_enc* ctx);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,14 @@ _SIGS = {
                                  C.c_int, C.c_int, _P]),
     "mx_snac_last_error": (C.c_char_p, [_P]),
     "mx_snac_destroy": (None, [_P]),
+    "mx_snac_enc_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
+    "mx_snac_enc_set_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int]),
+    "mx_snac_enc_finalize": (C.c_int, [_P]),
+    "mx_snac_enc_encode": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "mx_snac_enc_latent": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "mx_snac_enc_quantize": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mx_snac_enc_last_error": (C.c_char_p, [_P]),
+    "mx_snac_enc_destroy": (None, [_P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -24,8 +24,9 @@ DEFS = (["-DMX_ROWS_TRACE=1"] if TRACE else []) + \
     (os.environ.get("MORPHEUS_MX_DEFS", "").split() if VARIANT and not TRACE else [])
 SOURCES = ["capi.hip", "llm_kernels.hip", "rows_v4_dispatch.hip", "rows_v4_qkv.hip",
            "rows_v4_resid.hip", "rows_v4_silu.hip", "rows_v4_head.hip", "head_b1.hip",
-           "sample_kernels.hip", "snac_kernels.hip", "engine_b1.hip"]
-HEADERS = ["mx_common.h", "mx_llm_kernels.h", "mx_snac_kernels.h", "mx_rows_common.h",
+           "sample_kernels.hip", "snac_kernels.hip", "snac_enc_kernels.hip", "engine_b1.hip"]
+HEADERS = ["mx_common.h", "mx_llm_kernels.h", "mx_snac_kernels.h", "mx_snac_enc_kernels.h",
+           "mx_rows_common.h",
            "mx_rows_v4.inc", "mx_rows_v4_body.inc", "mx_engine.h"]
 ARCH = os.environ.get("MORPHEUS_MX_ARCH", "gfx950")
 

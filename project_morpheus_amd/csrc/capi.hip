@@ -15,6 +15,7 @@
 #include "mx_engine.h"
 #include "mx_llm_kernels.h"
 #include "mx_snac_kernels.h"
+#include "mx_snac_enc_kernels.h"
 
 using namespace mx;
 
@@ -2567,6 +2568,308 @@ extern "C" void mx_snac_destroy(mx_snac* s) {
   for (auto& kv : s->graphs) (void)hipGraphExecDestroy(kv.second);
   for (auto g : s->graph_defs) (void)hipGraphDestroy(g);
   if (s->cap) (void)hipStreamDestroy(s->cap);
+  for (void* p : s->allocs) (void)hipFree(p);
+  delete s;
+}
+
+// =====================================================================================
+// SNAC encoder context (mx_snac_enc_*): audio -> speechpipe frames.  A context of its own: the
+// decoder's buffers, graphs and addresses are untouched, and the codebooks (393 KB) are simply
+// held twice.  Launches per encode: 1 stem + 4 x (3 x (depthwise + 1x1) + down-conv) + output
+// depthwise + 3 quantiser levels = 33, enqueued eagerly on the caller's stream.
+// =====================================================================================
+static const int kEncRates[4] = {2, 4, 8, 8};
+static const int kEncMaxFrames = 4096;  // 2048 * 48 floats per frame: offsets stay below 2^31
+
+struct mx_snac_enc {
+  int device = 0;
+  int max_frames = 0;
+  std::string err;
+  std::map<std::string, float*> w;
+  std::map<std::string, int64_t> expect;
+  std::vector<void*> allocs;
+  std::map<std::string, uint16_t*> wbf;  // dense weights as bf16 planes [3][M][Kp]
+  float *cn[3] = {}, *cn2[3] = {};       // normalised codebooks and their squared lengths
+  float *bufA = nullptr, *bufB = nullptr, *bufS = nullptr;
+  bool final = false;
+};
+
+static void snac_enc_expect(mx_snac_enc* s) {
+  auto& e = s->expect;
+  e["enc.in.w"] = 48 * 7;
+  e["enc.in.b"] = 48;
+  for (int k = 0; k < 4; ++k) {
+    const int c = 48 << k;
+    const std::string p = "enc.b" + std::to_string(k) + ".";
+    for (int r = 0; r < 3; ++r) {
+      const std::string q = p + "r" + std::to_string(r) + ".";
+      e[q + "alpha1"] = c;
+      e[q + "dw.w"] = c * 7;
+      e[q + "dw.b"] = c;
+      e[q + "alpha2"] = c;
+      e[q + "pw.w"] = (int64_t)c * c;
+      e[q + "pw.b"] = c;
+    }
+    e[p + "alpha"] = c;
+    e[p + "down.w"] = (int64_t)2 * c * c * 2 * kEncRates[k];
+    e[p + "down.b"] = 2 * c;
+  }
+  e["enc.out.dw.w"] = 768 * 7;
+  e["enc.out.dw.b"] = 768;
+  for (int i = 0; i < 3; ++i) {
+    const std::string p = "q" + std::to_string(i) + ".";
+    e[p + "in_proj.w"] = 8 * 768;
+    e[p + "in_proj.b"] = 8;
+    e[p + "codebook"] = 4096 * 8;
+    e[p + "out_proj.w"] = 768 * 8;
+    e[p + "out_proj.b"] = 768;
+  }
+}
+
+extern "C" int mx_snac_enc_create(int device, int max_frames, mx_snac_enc** out) {
+  if (!out || max_frames < 1 || max_frames > kEncMaxFrames) {
+    g_err = "max_frames out of range";
+    return MX_ERR_ARG;
+  }
+  if (hipSetDevice(device) != hipSuccess) {
+    g_err = "hipSetDevice failed";
+    return MX_ERR_HIP;
+  }
+  auto* s = new mx_snac_enc();
+  s->device = device;
+  s->max_frames = max_frames;
+  snac_enc_expect(s);
+  *out = s;
+  return MX_OK;
+}
+
+extern "C" int mx_snac_enc_set_weight(mx_snac_enc* s, const char* name, const void* data,
+                                      int64_t numel, int dtype) {
+  if (!s || !name || !data) return MX_ERR_ARG;
+  if (dtype != MX_DTYPE_F32 && dtype != MX_DTYPE_BF16) MX_FAIL(s, MX_ERR_ARG, "bad dtype");
+  if (s->final) MX_FAIL(s, MX_ERR_STATE, "weights are frozen after mx_snac_enc_finalize");
+  const std::string n(name);
+  auto it = s->expect.find(n);
+  if (it == s->expect.end()) MX_FAIL(s, MX_ERR_ARG, "unknown snac encoder weight " + n);
+  if (it->second != numel) MX_FAIL(s, MX_ERR_ARG, n + ": bad numel");
+  MX_TRY(s, hipSetDevice(s->device));
+  float* d = nullptr;
+  auto f = s->w.find(n);
+  if (f == s->w.end()) {
+    void* p = nullptr;
+    MX_TRY(s, hipMalloc(&p, numel * 4 + 256));
+    s->allocs.push_back(p);
+    d = (float*)p;
+    s->w[n] = d;
+  } else {
+    d = f->second;
+  }
+  MX_TRY(s, launch_to_f32(d, data, numel, dtype == MX_DTYPE_BF16 ? 1 : 0, nullptr));
+  MX_TRY(s, hipDeviceSynchronize());
+  return MX_OK;
+}
+
+// fp32 [M][K] on the host -> three bf16 planes [3][M][Kp] on the device (zero columns past K)
+static int snac_enc_planes(mx_snac_enc* s, const std::string& name, const std::vector<float>& A,
+                           int M, int Kp) {
+  void *tmp = nullptr, *p = nullptr;
+  const size_t n = (size_t)M * Kp;
+  MX_TRY(s, hipMalloc(&tmp, n * 4));
+  hipError_t e = hipMemcpy(tmp, A.data(), n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(&p, n * 3 * 2);
+  if (e == hipSuccess) {
+    s->allocs.push_back(p);
+    s->wbf[name] = (uint16_t*)p;
+    e = launch_split_planes((const float*)tmp, (uint16_t*)p, (int64_t)n, nullptr);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  (void)hipFree(tmp);
+  MX_TRY(s, e);
+  return MX_OK;
+}
+
+extern "C" int mx_snac_enc_finalize(mx_snac_enc* s) {
+  if (!s) return MX_ERR_ARG;
+  if (s->final) MX_FAIL(s, MX_ERR_STATE, "already finalized");
+  for (auto& kv : s->expect)
+    if (!s->w.count(kv.first)) MX_FAIL(s, MX_ERR_STATE, "missing snac encoder weight " + kv.first);
+  MX_TRY(s, hipSetDevice(s->device));
+  for (int k = 0; k < 4; ++k) {
+    const int c = 48 << k, taps = 2 * kEncRates[k];
+    const std::string p = "enc.b" + std::to_string(k) + ".";
+    const int Kp = (c + 31) / 32 * 32;  // C = 48: two 32-deep MFMA steps, the last 16 columns zero
+    std::vector<float> W, A;
+    for (int r = 0; r < 3; ++r) {
+      const std::string name = p + "r" + std::to_string(r) + ".pw.w";
+      W.resize((size_t)c * c);
+      MX_TRY(s, hipMemcpy(W.data(), s->w[name], W.size() * 4, hipMemcpyDeviceToHost));
+      A.assign((size_t)c * Kp, 0.f);
+      for (int m = 0; m < c; ++m)
+        for (int ci = 0; ci < c; ++ci) A[(size_t)m * Kp + ci] = W[(size_t)m * c + ci];
+      const int rc = snac_enc_planes(s, name, A, c, Kp);
+      if (rc != MX_OK) return rc;
+    }
+    // Conv1d weight [2C][C][taps] -> [2C][tap][C]: the K order of a channels-last input run
+    const std::string name = p + "down.w";
+    const int K = taps * c;
+    W.resize((size_t)2 * c * K);
+    MX_TRY(s, hipMemcpy(W.data(), s->w[name], W.size() * 4, hipMemcpyDeviceToHost));
+    A.assign(W.size(), 0.f);
+    for (int m = 0; m < 2 * c; ++m)
+      for (int ci = 0; ci < c; ++ci)
+        for (int j = 0; j < taps; ++j)
+          A[(size_t)m * K + (size_t)j * c + ci] = W[((size_t)m * c + ci) * taps + j];
+    const int rc = snac_enc_planes(s, name, A, 2 * c, K);
+    if (rc != MX_OK) return rc;
+  }
+  for (int i = 0; i < 3; ++i) {
+    void* p = nullptr;
+    MX_TRY(s, hipMalloc(&p, (size_t)4096 * 9 * 4));
+    s->allocs.push_back(p);
+    s->cn[i] = (float*)p;
+    s->cn2[i] = s->cn[i] + 4096 * 8;
+    MX_TRY(s, launch_enc_codebook_norm(s->w["q" + std::to_string(i) + ".codebook"], s->cn[i],
+                                       s->cn2[i], nullptr));
+  }
+  // activations: x, scratch and Snake(x), each sized by the full-rate 48-channel stage
+  const size_t elems = (size_t)2048 * 48 * s->max_frames;
+  for (float** b : {&s->bufA, &s->bufB, &s->bufS}) {
+    void* p = nullptr;
+    if (hipMalloc(&p, elems * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      MX_FAIL(s, MX_ERR_OOM, "snac encoder buffers: allocation failed");
+    }
+    s->allocs.push_back(p);
+    *b = (float*)p;
+  }
+  MX_TRY(s, hipDeviceSynchronize());
+  s->final = true;
+  return MX_OK;
+}
+
+// Waves splitting K in one run conv-GEMM tile: the deep down-convs (K = 3,072 and 6,144) have few
+// output columns and a long serial K loop per wave, so their K is split while a wave keeps at
+// least six 32-deep steps and the launch stays within ~8k waves.
+static int snac_enc_pick_wk(int M, int Kp, int Tout) {
+  const int tiles = (M / 48) * ((Tout + 31) / 32), steps = Kp / 32;
+  int wk = 1;
+  while (wk < 8 && steps % (2 * wk) == 0 && steps / (2 * wk) >= 6 && tiles * wk * 2 <= 16384) wk *= 2;
+  return wk;
+}
+
+// audio -> z [4 n_frames][768] in bufB
+static int snac_enc_latent_enqueue(mx_snac_enc* s, const float* audio, int64_t n_samples,
+                                   int n_frames, hipStream_t st) {
+  auto W = [&](const std::string& n) { return s->w.at(n); };
+  float *A = s->bufA, *Bf = s->bufB, *S = s->bufS;
+  int T = 2048 * n_frames;
+  MX_TRY(s, launch_enc_stem(audio, n_samples, W("enc.in.w"), W("enc.in.b"), A, T, st));
+  for (int k = 0; k < 4; ++k) {
+    const int c = 48 << k, sr = kEncRates[k];
+    const std::string p = "enc.b" + std::to_string(k) + ".";
+    for (int r = 0; r < 3; ++r) {  // ResidualUnit(d): A += pw(Snake(dw_d(Snake(A))))
+      const std::string q = p + "r" + std::to_string(r) + ".";
+      if (c % 64)
+        MX_TRY(s, launch_enc_dwconv(A, Bf, W(q + "dw.w"), W(q + "dw.b"), W(q + "alpha1"),
+                                    W(q + "alpha2"), c, T, kDil[r], st));
+      else
+        MX_TRY(s, launch_dwconv(A, Bf, W(q + "dw.w"), W(q + "dw.b"), W(q + "alpha1"),
+                                W(q + "alpha2"), 1, c, T, kDil[r], st));
+      EncGemmArgs g{};
+      g.A = s->wbf.at(q + "pw.w"); g.X = Bf; g.bias = W(q + "pw.b"); g.R = A; g.out = A;
+      g.M = c; g.K = c; g.Kp = (c + 31) / 32 * 32; g.C = c; g.Tin = T; g.Tout = T;
+      g.stride = 1; g.pad = 0;
+      if (r == 2) {  // the block's closing Snake, for the down-conv
+        g.out2 = S;
+        g.alpha2 = W(p + "alpha");
+      }
+      g.wk = snac_enc_pick_wk(g.M, g.Kp, g.Tout);
+      MX_TRY(s, launch_enc_gemm(g, st));
+    }
+    EncGemmArgs g{};  // Conv1d(C -> 2C, k = 2 sr, stride sr, pad ceil(sr / 2)) on Snake(x)
+    g.A = s->wbf.at(p + "down.w"); g.X = S; g.bias = W(p + "down.b"); g.out = A;
+    g.M = 2 * c; g.K = 2 * sr * c; g.Kp = g.K; g.C = c; g.Tin = T; g.Tout = T / sr;
+    g.stride = sr; g.pad = (sr + 1) / 2;
+    g.wk = snac_enc_pick_wk(g.M, g.Kp, g.Tout);
+    MX_TRY(s, launch_enc_gemm(g, st));
+    T /= sr;
+  }
+  MX_TRY(s, launch_dwconv(A, Bf, W("enc.out.dw.w"), W("enc.out.dw.b"), nullptr, nullptr, 1, 768, T,
+                          1, st));
+  return MX_OK;
+}
+
+// bufB (z, consumed as the residual) -> frames
+static int snac_enc_quant_enqueue(mx_snac_enc* s, int n_frames, int32_t* frames, hipStream_t st) {
+  for (int i = 0; i < 3; ++i) {
+    const std::string p = "q" + std::to_string(i) + ".";
+    EncQuantArgs q{};
+    q.res = s->bufB; q.in_w = s->w.at(p + "in_proj.w"); q.in_b = s->w.at(p + "in_proj.b");
+    q.cn = s->cn[i]; q.cn2 = s->cn2[i]; q.cb = s->w.at(p + "codebook");
+    q.out_w = s->w.at(p + "out_proj.w"); q.out_b = s->w.at(p + "out_proj.b");
+    q.frames = frames; q.n_frames = n_frames; q.level = i;
+    MX_TRY(s, launch_enc_quant(q, st));
+  }
+  return MX_OK;
+}
+
+// every check of an audio call, before anything is enqueued; -> n_frames through *nf
+static int snac_enc_check_audio(mx_snac_enc* s, const void* audio, int64_t n_samples,
+                                const void* out, int* nf) {
+  if (!audio || !out) MX_FAIL(s, MX_ERR_ARG, "null pointer");
+  if (!s->final) MX_FAIL(s, MX_ERR_STATE, "not finalized");
+  if (n_samples < 1) MX_FAIL(s, MX_ERR_ARG, "n_samples < 1");
+  const int64_t n = (n_samples + 2047) / 2048;
+  if (n > s->max_frames) MX_FAIL(s, MX_ERR_ARG, "audio longer than max_frames");
+  *nf = (int)n;
+  return MX_OK;
+}
+
+extern "C" int mx_snac_enc_encode(mx_snac_enc* s, const float* audio, int64_t n_samples,
+                                  int32_t* frames_out, void* stream) {
+  if (!s) return MX_ERR_ARG;
+  int nf = 0;
+  int rc = snac_enc_check_audio(s, audio, n_samples, frames_out, &nf);
+  if (rc != MX_OK) return rc;
+  MX_TRY(s, hipSetDevice(s->device));
+  rc = snac_enc_latent_enqueue(s, audio, n_samples, nf, (hipStream_t)stream);
+  if (rc != MX_OK) return rc;
+  return snac_enc_quant_enqueue(s, nf, frames_out, (hipStream_t)stream);
+}
+
+extern "C" int mx_snac_enc_latent(mx_snac_enc* s, const float* audio, int64_t n_samples,
+                                  float* z_out, void* stream) {
+  if (!s) return MX_ERR_ARG;
+  int nf = 0;
+  int rc = snac_enc_check_audio(s, audio, n_samples, z_out, &nf);
+  if (rc != MX_OK) return rc;
+  MX_TRY(s, hipSetDevice(s->device));
+  rc = snac_enc_latent_enqueue(s, audio, n_samples, nf, (hipStream_t)stream);
+  if (rc != MX_OK) return rc;
+  MX_TRY(s, hipMemcpyAsync(z_out, s->bufB, (size_t)nf * 4 * 768 * 4, hipMemcpyDefault,
+                           (hipStream_t)stream));
+  return MX_OK;
+}
+
+extern "C" int mx_snac_enc_quantize(mx_snac_enc* s, const float* z, int n_frames,
+                                    int32_t* frames_out, void* stream) {
+  if (!s) return MX_ERR_ARG;
+  if (!z || !frames_out) MX_FAIL(s, MX_ERR_ARG, "null pointer");
+  if (!s->final) MX_FAIL(s, MX_ERR_STATE, "not finalized");
+  if (n_frames < 1 || n_frames > s->max_frames) MX_FAIL(s, MX_ERR_ARG, "n_frames out of range");
+  MX_TRY(s, hipSetDevice(s->device));
+  MX_TRY(s, hipMemcpyAsync(s->bufB, z, (size_t)n_frames * 4 * 768 * 4, hipMemcpyDefault,
+                           (hipStream_t)stream));
+  return snac_enc_quant_enqueue(s, n_frames, frames_out, (hipStream_t)stream);
+}
+
+extern "C" const char* mx_snac_enc_last_error(const mx_snac_enc* s) {
+  return s ? s->err.c_str() : g_err.c_str();
+}
+
+extern "C" void mx_snac_enc_destroy(mx_snac_enc* s) {
+  if (!s) return;
+  (void)hipSetDevice(s->device);
   for (void* p : s->allocs) (void)hipFree(p);
   delete s;
 }

@@ -6,6 +6,16 @@
 
 namespace mx {
 
+__device__ __forceinline__ float snake(float x, float a) {
+  // layers.py snake(): x + (alpha + 1e-9).reciprocal() * sin(alpha * x)^2.  The sine is the
+  // hardware v_sin_f32 (8 cycles) on the fp32 argument reduced to [0, 1) revolutions: the
+  // library sinf (~30 instructions) made the Snake stages VALU-bound.  CPU emulation of this
+  // reduction: audio RMS 6e-7 vs torch.sin (scripts/snac_fastsin_emulation.py).
+  const float rev = (a * x) * 0.15915494309189535f;
+  const float s = __builtin_amdgcn_sinf(rev - floorf(rev));
+  return x + (1.0f / (a + 1e-9f)) * (s * s);
+}
+
 enum { CG_STORE = 0, CG_RESID = 1, CG_NOISE = 2 };
 
 struct ConvGemmArgs {

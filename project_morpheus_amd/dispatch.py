@@ -90,6 +90,14 @@ def _worker(device: int, inbox, outbox, factory: Callable, content_seed: int = 0
                 err = e
             if err is not None:
                 outbox.put(("prefix", -1, (device, name, repr(err))))
+        elif kind == "voice_ids":
+            # encode a reference recording here; rank 0 registers the ids on every worker
+            _, rid, text, audio, sample_rate = msg
+            try:
+                outbox.put(("chunk", rid, svc.voice_prefix_ids(text, audio, sample_rate)))
+                outbox.put(("end", rid, None))
+            except BaseException as e:
+                outbox.put(("end", rid, repr(e)))
         elif kind == "cancel":
             with lock:
                 h = handles.get(msg[1])
@@ -265,6 +273,32 @@ class GpuPool:
             for w in sent:
                 self.inboxes[w].put(("register_prefix", name, ids))
         return sent
+
+    def voice_prefix_ids(self, text: str, audio, sample_rate: int = I.SAMPLE_RATE,
+                         timeout: Optional[float] = 120.0) -> List[int]:
+        """The framed ids of the voice prompt (text, audio), encoded by ONE worker
+        (``Service.voice_prefix_ids``); ValueError with the worker's message if it refuses."""
+        import numpy as np
+        audio = np.ascontiguousarray(audio.cpu().numpy() if hasattr(audio, "cpu") else audio)
+        h = self._enqueue(0, lambda rid: ("voice_ids", rid, text, audio, int(sample_rate)))
+        try:
+            ids = h.get(timeout=timeout)
+            if ids is not None:
+                h.get(timeout=timeout)
+        except RuntimeError as e:
+            raise ValueError(str(e)) from e
+        return [int(t) for t in ids]
+
+    def register_voice(self, name: str, text: str, audio,
+                       sample_rate: int = I.SAMPLE_RATE) -> List[int]:
+        """Register a cloned voice from a recording: one worker encodes it and returns the ids,
+        then ``register_prefix`` as for any prefix -- so every worker, and one respawned later,
+        gets the ids, not the audio.  -> the workers the prefix was sent to."""
+        from .batching import check_prefix
+        check_prefix(name)
+        if not name:
+            raise ValueError("voice name must be a non-empty string")
+        return self.register_prefix(name, self.voice_prefix_ids(text, audio, sample_rate))
 
     def unregister_prefix(self, name: str) -> None:
         with self._lock:

@@ -4,6 +4,8 @@
                   engine_class.py:117, and llama.cpp ``Llama``, llama_local.py:42-52).
 * ``SnacDecoder`` wraps mx_snac_* (replaces ``SNAC.decode`` + slice + PCM16,
                   speechpipe.py:76-129).
+* ``SnacEncoder`` wraps mx_snac_enc_* (replaces ``SNAC.encode`` of the third-party snac
+                  package: reference audio -> the speech codes of a voice prompt).
 * ``Synthesizer`` is the Orpheus decoder loop (engine_class.py:103-134 +
                   speechpipe.py:191-337) at the token-id level: prefill, hipGraph decode
                   steps kept ``depth`` deep in the GPU queue, the reference's window schedule
@@ -383,6 +385,104 @@ class SnacDecoder:
     def close(self):
         if getattr(self, "h", None):
             self.lib.mx_snac_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SnacEncoder:
+    """One mx_snac_enc context (fp32 SNAC 24 kHz encoder + residual vector quantiser): mono
+    24 kHz audio -> speechpipe frames.  ``weights``: ``weights.snac_encoder_shapes`` plus the
+    codebooks and output projections of ``weights.snac_shapes`` (other keys are ignored, so a
+    ``load_snac_state_dict(path, encoder=True)`` dict can be handed in whole)."""
+
+    def __init__(self, weights: Dict[str, torch.Tensor], device: int = 0, max_frames: int = 384):
+        from .weights import snac_encoder_shapes
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device, self.max_frames = device, max_frames
+        h = C.c_void_p()
+        torch.cuda.set_device(device)
+        _lib.check(self.lib.mx_snac_enc_create(device, max_frames, C.byref(h)),
+                   self.lib.mx_snac_enc_last_error, None)
+        self.h = h
+        dev = torch.device("cuda", device)
+        names = list(snac_encoder_shapes()) + [f"q{i}.{n}" for i in range(3)
+                                                for n in ("codebook", "out_proj.w", "out_proj.b")]
+        for name in names:
+            td = weights[name].to(dev).contiguous()
+            self._check(self.lib.mx_snac_enc_set_weight(h, name.encode(),
+                                                        C.c_void_p(td.data_ptr()), td.numel(),
+                                                        _dtype_code(td)))
+        self._check(self.lib.mx_snac_enc_finalize(h))
+        torch.cuda.synchronize(device)
+
+    def _check(self, rc):
+        _lib.check(rc, self.lib.mx_snac_enc_last_error, self.h)
+
+    def _audio(self, audio) -> torch.Tensor:
+        """float samples in [-1, 1] or int16 PCM (/ 32768), host or device -> fp32 [n] on the GPU."""
+        a = torch.as_tensor(audio)
+        if a.dtype == torch.int16:
+            a = a.to(torch.float32) / 32768.0
+        elif not a.dtype.is_floating_point:
+            raise TypeError(f"audio must be float or int16 PCM, not {a.dtype}")
+        return a.reshape(-1).to(torch.device("cuda", self.device), torch.float32).contiguous()
+
+    @staticmethod
+    def n_frames(n_samples: int) -> int:
+        return -(-n_samples // SAMPLES_PER_FRAME)
+
+    def encode(self, audio, stream=None) -> torch.Tensor:
+        """-> int32 [n_frames, 7] (device) in speechpipe order."""
+        stream = stream or torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            a = self._audio(audio)
+            frames = torch.empty(max(self.n_frames(a.numel()), 1), 7, dtype=torch.int32,
+                                 device=a.device)
+        self._check(self.lib.mx_snac_enc_encode(self.h, C.c_void_p(a.data_ptr()), a.numel(),
+                                                C.c_void_p(frames.data_ptr()),
+                                                C.c_void_p(stream.cuda_stream)))
+        a.record_stream(stream)
+        frames.record_stream(stream)
+        return frames
+
+    def latent(self, audio, stream=None) -> torch.Tensor:
+        """-> the encoder's latent z, fp32 [4 * n_frames, 768] (channels-last, device)."""
+        stream = stream or torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            a = self._audio(audio)
+            z = torch.empty(4 * max(self.n_frames(a.numel()), 1), 768, dtype=torch.float32,
+                            device=a.device)
+        self._check(self.lib.mx_snac_enc_latent(self.h, C.c_void_p(a.data_ptr()), a.numel(),
+                                                C.c_void_p(z.data_ptr()),
+                                                C.c_void_p(stream.cuda_stream)))
+        a.record_stream(stream)
+        z.record_stream(stream)
+        return z
+
+    def quantize(self, z, stream=None) -> torch.Tensor:
+        """z fp32 [4 * n_frames, 768] -> int32 [n_frames, 7]: the quantiser alone."""
+        stream = stream or torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            z = torch.as_tensor(z).to(torch.device("cuda", self.device), torch.float32).contiguous()
+            if z.dim() != 2 or z.shape[1] != 768 or z.shape[0] % 4 or not z.shape[0]:
+                raise ValueError(f"z must be [4 * n_frames, 768], not {tuple(z.shape)}")
+            frames = torch.empty(z.shape[0] // 4, 7, dtype=torch.int32, device=z.device)
+        self._check(self.lib.mx_snac_enc_quantize(self.h, C.c_void_p(z.data_ptr()),
+                                                  z.shape[0] // 4, C.c_void_p(frames.data_ptr()),
+                                                  C.c_void_p(stream.cuda_stream)))
+        z.record_stream(stream)
+        frames.record_stream(stream)
+        return frames
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mx_snac_enc_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -108,6 +108,26 @@ def frame_voice_pairs(pairs: Iterable) -> List[int]:
     return out
 
 
+AUDIO_CODE_BASE = 128266  # id of code 0 at frame position 0 (custom token 10)
+
+
+def audio_ids_from_frames(frames) -> List[int]:
+    """SNAC frames ``[n_frames][7]`` in speechpipe order (``SnacEncoder.encode``) -> the
+    audio-token ids of a voice prompt: id = 128266 + 4096 k + code for position k of a frame,
+    the inverse of ``schedule.code_of_id``."""
+    rows = frames.tolist() if hasattr(frames, "tolist") else list(frames)
+    out: List[int] = []
+    for row in rows:
+        if len(row) != 7:
+            raise ValueError("a SNAC frame has 7 codes")
+        for k, code in enumerate(row):
+            code = int(code)
+            if not 0 <= code < 4096:
+                raise ValueError(f"SNAC code {code} outside 0..4095")
+            out.append(AUDIO_CODE_BASE + 4096 * k + code)
+    return out
+
+
 def split_text_into_sentences(text: str) -> List[str]:
     """Sentence split: a whitespace char after . ! ? ends a sentence unless the char two
     back is '.' or ' ' (abbreviation heuristic); pieces < 20 chars merge forward."""

@@ -85,14 +85,61 @@ def _service_tokens(prompt_ids, **params):
     return get_service().submit_tokens(prompt_ids, **params)
 
 
+def parse_voice_wav(data: bytes):
+    """RIFF WAV bytes -> (int16 mono samples, sample rate).  ValueError on anything but PCM16
+    mono at 24 kHz with at least one sample (there is no resampler and no down-mix)."""
+    import numpy as np
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError("audio is not a RIFF WAVE file")
+    fmt, pcm, off = None, None, 12
+    while off + 8 <= len(data):
+        tag, size = data[off:off + 4], struct.unpack_from("<I", data, off + 4)[0]
+        body = data[off + 8:off + 8 + size]   # (a streamed header's 0xFFFFFFFF: up to the end)
+        if tag == b"fmt " and len(body) >= 16:
+            fmt = struct.unpack_from("<HHIIHH", body)
+        elif tag == b"data":
+            pcm = body
+            break
+        off += 8 + size + (size & 1)
+    if fmt is None or pcm is None:
+        raise ValueError("WAV lacks a fmt or data chunk")
+    code, channels, rate, _, _, bits = fmt
+    if code != 1 or bits != 16:
+        raise ValueError(f"WAV must be 16-bit PCM (format {code}, {bits} bits)")
+    if channels != 1:
+        raise ValueError(f"WAV must be mono ({channels} channels)")
+    if rate != I.SAMPLE_RATE:
+        raise ValueError(f"WAV must be {I.SAMPLE_RATE} Hz ({rate} Hz; there is no resampler)")
+    samples = np.frombuffer(pcm[:len(pcm) // 2 * 2], dtype="<i2")
+    if samples.size < 1:
+        raise ValueError("WAV holds no samples")
+    return samples, rate
+
+
+def service_voice_registrar(name: str, text: str, samples, sample_rate: int) -> int:
+    """``voice_registrar`` over the process' service (``Service`` or ``GpuPool``): encode,
+    frame, register; -> the number of prefix ids."""
+    from .service import get_service
+    svc = get_service()
+    ids = svc.voice_prefix_ids(text, samples, sample_rate)
+    h = svc.register_prefix(name, ids)
+    if hasattr(h, "result"):
+        h.result(timeout=120.0)
+    return len(ids)
+
+
 def build_app(adapter_cls=None, token_source=_service_tokens, encode=None,
               decode=None, orchestrated_stream=None,
-              registry: Optional[AdapterRegistry] = None) -> Starlette:
+              registry: Optional[AdapterRegistry] = None, voice_registrar=None) -> Starlette:
     """``adapter_cls`` (tests / bench): the class registered as ``mi355x`` (default
     ``MxTTSAdapter``).  ``token_source(prompt_ids, **params)`` backs /v1/completions (default:
     this GPU's service); ``encode`` / ``decode`` default to the process tokenizer.
     ``orchestrated_stream(adapter)``: the control plane's PCM stream over an adapter (module
-    docstring); None = plain 4096-byte pulls."""
+    docstring); None = plain 4096-byte pulls.
+    ``voice_registrar(name, text, int16 samples, sample_rate) -> number of prefix ids``
+    (``service_voice_registrar``): with it the app serves ``POST /v1/voices`` {"name", "text",
+    "audio_b64": RIFF WAV, PCM16 mono 24 kHz} -> {"name", "frames", "prefix_ids"}, registering a
+    cloned voice that requests name as their prefix; without it the route does not exist."""
     from .completions import build_route
     from .tokenizer import default_tokenizer
     if encode is None:
@@ -181,7 +228,28 @@ def build_app(adapter_cls=None, token_source=_service_tokens, encode=None,
         return JSONResponse({"message": "ok", "adapter": state["adapter"],
                              "voice": state["voice"].model_dump()})
 
-    return Starlette(routes=[Route("/v1/audio/speech", speech, methods=["POST"]),
+    async def register_voice(request: Request) -> JSONResponse:
+        import base64
+        import binascii
+        try:
+            data = await request.json()
+            name, text, b64 = data["name"], data["text"], data["audio_b64"]
+            if not all(isinstance(v, str) and v for v in (name, text, b64)):
+                raise ValueError("name, text and audio_b64 must be non-empty strings")
+            samples, rate = parse_voice_wav(base64.b64decode(b64, validate=True))
+        except (KeyError, TypeError) as exc:
+            raise HTTPException(status_code=400, detail=f"missing field {exc}") from exc
+        except (ValueError, binascii.Error) as exc:
+            raise HTTPException(status_code=400, detail=str(exc)) from exc
+        try:
+            n_ids = voice_registrar(name, text, samples, rate)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc)) from exc
+        return JSONResponse({"name": name, "frames": -(-int(samples.size) // 2048),
+                             "prefix_ids": int(n_ids)})
+
+    extra = [Route("/v1/voices", register_voice, methods=["POST"])] if voice_registrar else []
+    return Starlette(routes=extra + [Route("/v1/audio/speech", speech, methods=["POST"]),
                              Route("/v1/completions", build_route(token_source, encode, decode),
                                    methods=["POST"]),
                              Route("/v1/audio/voices", voices, methods=["GET"]),
@@ -203,4 +271,11 @@ def configured_stream():
     return getattr(importlib.import_module(mod), name)
 
 
-app: Optional[Starlette] = build_app(orchestrated_stream=configured_stream())
+def configured_voice_registrar():
+    """``service_voice_registrar`` when ``MORPHEUS_MX_VOICES=1`` (the module-level ``app`` then
+    serves ``POST /v1/voices``), else None: the route does not exist."""
+    return service_voice_registrar if os.environ.get("MORPHEUS_MX_VOICES", "0") == "1" else None
+
+
+app: Optional[Starlette] = build_app(orchestrated_stream=configured_stream(),
+                                     voice_registrar=configured_voice_registrar())

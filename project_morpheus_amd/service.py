@@ -26,10 +26,12 @@ from . import config as C
 from . import inference as I
 from .batching import (BatchSynthesizer, StreamHandle, StreamRequest, UnknownPrefix,
                        check_prefix)
-from .engine import LlmEngine, SnacDecoder
+from .engine import SAMPLES_PER_FRAME, LlmEngine, SnacDecoder, SnacEncoder
 from .tokenizer import Tokenizer, default_tokenizer
 from .weights import (load_hf_llm, load_snac_state_dict, synthetic_llm_weights,
-                      synthetic_snac_weights)
+                      synthetic_snac_encoder_weights, synthetic_snac_weights)
+
+VOICE_MAX_FRAMES = 384  # 32 s of reference audio: the largest encoder context a service builds
 
 
 class Service:
@@ -37,8 +39,12 @@ class Service:
                  llm_weights=None, snac_weights=None, max_pos: int = 2048,
                  tokenizer: Optional[Tokenizer] = None, max_prefill: int = 512,
                  max_batch: int = C.MX_MAX_SLOTS, synthetic_audio: Optional[bool] = None,
-                 packed_prefill: Optional[bool] = None, prefix_slots: Optional[int] = None):
-        """``prefix_slots``: template KV slots for registered prefixes (``register_prefix``;
+                 packed_prefill: Optional[bool] = None, prefix_slots: Optional[int] = None,
+                 snac_encoder_weights=None):
+        """``snac_encoder_weights``: the SNAC encoder's weights (``weights.snac_encoder_shapes``)
+        for ``register_voice`` / ``encode_audio``; None: from MORPHEUS_MX_SNAC, synthetic when
+        unset.  The encoder is built at first use, nothing is allocated for it before.
+        ``prefix_slots``: template KV slots for registered prefixes (``register_prefix``;
         None: MORPHEUS_MX_PREFIX_SLOTS, 0 when unset -- nothing is allocated for them then).
         ``synthetic_audio``: feed the SNAC schedule a seeded audio-code stream per request
         (default: whenever the LLM weights are synthetic, which never speak).
@@ -65,6 +71,9 @@ class Service:
                              max_pos=max_pos, max_batch=max_batch, max_prefill=max_prefill)
         del llm_weights
         self.snac = SnacDecoder(snac_weights, device=device, max_batch=max_batch)
+        # the quantiser searches the codebooks the decoder embeds with
+        self._vq_weights = {k: v for k, v in snac_weights.items() if k.startswith("q")}
+        self._enc_weights = snac_encoder_weights
         self.batch = BatchSynthesizer(self.llm, self.snac, packed_prefill=packed_prefill,
                                       prefix_slots=prefix_slots).start()
         self.tok = tokenizer or default_tokenizer()
@@ -97,6 +106,81 @@ class Service:
 
     def unregister_prefix(self, name: str):
         return self.batch.unregister_prefix(name)
+
+    # ------------------------------------------------------------------ voice prompts from audio
+    def _voice_encoder(self) -> SnacEncoder:
+        """The SNAC encoder, built at first use (call under ``_enc_lock``)."""
+        enc = getattr(self, "_enc", None)
+        if enc is None:
+            w = getattr(self, "_enc_weights", None)
+            if w is None:
+                if C.MX_SNAC:
+                    w = load_snac_state_dict(C.MX_SNAC, encoder=True)
+                else:
+                    warnings.warn("MORPHEUS_MX_SNAC unset: seeded SYNTHETIC SNAC encoder weights")
+                    w = synthetic_snac_encoder_weights()
+            vq = getattr(self, "_vq_weights", None) or synthetic_snac_weights()
+            w = {**{k: v for k, v in vq.items() if k.startswith("q")}, **w}
+            enc = self._enc = SnacEncoder(w, device=self.device, max_frames=self.voice_max_frames)
+            self._enc_stream = torch.cuda.Stream(self.device)
+        return enc
+
+    @property
+    def voice_max_frames(self) -> int:
+        """Frames of reference audio one voice prompt may hold: what fits ``max_pos`` as ids,
+        at most ``VOICE_MAX_FRAMES``."""
+        return max(1, min(VOICE_MAX_FRAMES, (self.llm.max_pos - 9) // 7))
+
+    def _check_audio(self, audio, sample_rate: int) -> int:
+        """-> frames the audio encodes to; ValueError on what no encode is tried for."""
+        if int(sample_rate) != I.SAMPLE_RATE:
+            raise ValueError(f"voice audio must be {I.SAMPLE_RATE} Hz mono, got {sample_rate} Hz "
+                             "(there is no resampler)")
+        n = int(np.prod(tuple(audio.shape))) if hasattr(audio, "shape") else len(audio)
+        if n < 1:
+            raise ValueError("voice audio is empty")
+        frames = -(-n // SAMPLES_PER_FRAME)
+        if frames > self.voice_max_frames:
+            raise ValueError(f"voice audio of {frames} frames exceeds {self.voice_max_frames} "
+                             f"({self.voice_max_frames * SAMPLES_PER_FRAME / I.SAMPLE_RATE:.1f} s)")
+        return frames
+
+    def encode_audio(self, audio, sample_rate: int = I.SAMPLE_RATE):
+        """Mono 24 kHz audio (float in [-1, 1] or int16 PCM; numpy or torch, host or device) ->
+        its audio-token ids (``inference.audio_ids_from_frames`` of the SNAC encoder's frames).
+        Runs in the caller's thread on the encoder's own HIP stream, one encode at a time."""
+        self._check_audio(audio, sample_rate)
+        with _enc_lock:
+            enc = self._voice_encoder()
+            frames = enc.encode(audio, stream=self._enc_stream)
+            self._enc_stream.synchronize()
+        return I.audio_ids_from_frames(frames.cpu())
+
+    def voice_prefix_ids(self, text: str, audio, sample_rate: int = I.SAMPLE_RATE):
+        """The framed ids of the voice prompt (text, audio): ``frame_voice_pairs([(text ids,
+        audio ids)])``.  ValueError, before anything is encoded, on a sample rate other than
+        24,000, empty audio, audio beyond ``voice_max_frames``, or a framed prompt that would
+        not fit ``max_pos``."""
+        frames = self._check_audio(audio, sample_rate)
+        text_ids = self.tok.encode(text)
+        if not text_ids:
+            raise ValueError("a voice prompt needs its transcript")
+        n = len(I.frame_voice_pairs([(text_ids, [0])])) - 1 + 7 * frames
+        if n >= self.llm.max_pos - 1:
+            raise ValueError(f"voice prompt of {n} ids does not fit (max_pos {self.llm.max_pos}: "
+                             "it needs room for a suffix and a token)")
+        return I.frame_voice_pairs([(text_ids, self.encode_audio(audio, sample_rate))])
+
+    def register_voice(self, name: str, text: str, audio, sample_rate: int = I.SAMPLE_RATE):
+        """Register a cloned voice from a recording and its transcript: encode ``audio``, frame
+        it with ``text`` and ``register_prefix`` the result under ``name`` -> that handle.
+        Requests then name it with ``submit(prefix=name)``."""
+        check_prefix(name)
+        if not name:
+            raise ValueError("voice name must be a non-empty string")
+        if self.batch.prefix_slots < 1:
+            raise ValueError("no template slots (prefix_slots is 0)")
+        return self.register_prefix(name, self.voice_prefix_ids(text, audio, sample_rate))
 
     def _check_prefix(self, prefix) -> None:
         """Refused at submit time (ValueError: HTTP 400): a prefix that is no name, or that
@@ -182,8 +266,12 @@ class Service:
 
     def close(self) -> None:
         self.batch.stop()
+        enc = getattr(self, "_enc", None)
+        if enc is not None:
+            enc.close()
 
 
+_enc_lock = threading.Lock()   # one voice encode at a time per process
 _service: Optional[Service] = None
 _service_lock = threading.Lock()
 

@@ -10,7 +10,8 @@ matrices, unit norms, bf16).  Real weights load from local paths only:
   ``snac.SNAC`` (``decoder.model.{i}...``), weight norm folded here:
   w = g * v / ||v|| over every dim but 0 (torch weight_norm, dim=0).
   The key mapping follows snac 1.2.x's module tree and is UNVERIFIED until a checkpoint
-  is supplied.
+  is supplied.  ``encoder=True`` also maps the encoder (``encoder.block.{i}...``)
+  and the quantiser's input projections, for ``engine.SnacEncoder``.
 """
 from __future__ import annotations
 
@@ -178,13 +179,58 @@ def synthetic_snac_weights(seed: int = 3) -> Dict[str, torch.Tensor]:
     return out
 
 
+SNAC_ENC_RATES = (2, 4, 8, 8)
+
+
+def snac_encoder_shapes() -> Dict[str, tuple]:
+    """The encoder half of SNAC 24 kHz and the quantiser's input projections (``SnacEncoder``;
+    the codebooks and output projections it also needs are in ``snac_shapes``)."""
+    s = {"enc.in.w": (48, 1, 7), "enc.in.b": (48,)}
+    for k, r in enumerate(SNAC_ENC_RATES):
+        c = 48 << k
+        p = f"enc.b{k}."
+        for j in range(3):
+            q = f"{p}r{j}."
+            s.update({q + "alpha1": (c,), q + "dw.w": (c, 1, 7), q + "dw.b": (c,),
+                      q + "alpha2": (c,), q + "pw.w": (c, c), q + "pw.b": (c,)})
+        s.update({p + "alpha": (c,), p + "down.w": (2 * c, c, 2 * r), p + "down.b": (2 * c,)})
+    s.update({"enc.out.dw.w": (768, 1, 7), "enc.out.dw.b": (768,)})
+    for i in range(3):
+        s[f"q{i}.in_proj.w"] = (8, 768)
+        s[f"q{i}.in_proj.b"] = (8,)
+    return s
+
+
+def synthetic_snac_encoder_weights(seed: int = 5) -> Dict[str, torch.Tensor]:
+    """fp32 CPU weights for ``snac_encoder_shapes`` with ``synthetic_snac_weights``' scaling:
+    fan-in scaled matrices, gain 0.3 on the residual units' 1x1 convs, biases 0.02 randn,
+    alpha 1 + 0.5 rand.  On audio of amplitude ~0.3 the latent comes out with RMS ~1."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for name, shape in snac_encoder_shapes().items():
+        leaf = name.rsplit(".", 1)[-1]
+        if "alpha" in leaf:
+            w = 1.0 + 0.5 * torch.rand(shape, generator=g)
+        elif leaf == "b":
+            w = 0.02 * torch.randn(shape, generator=g)
+        else:
+            gain = 0.3 if ".pw.w" in name else 1.0
+            w = gain * torch.randn(shape, generator=g) / math.sqrt(math.prod(shape[1:]))
+        out[name] = w.float().contiguous()
+    return out
+
+
 def fold_weight_norm(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     dims = tuple(range(1, v.dim()))
     return (g * v / v.norm(dim=dims, keepdim=True)).float()
 
 
-def load_snac_state_dict(path: str) -> Dict[str, torch.Tensor]:
-    """Map a snac 1.2.x SNAC state dict (24 kHz) onto the build's SNAC weight names."""
+def load_snac_state_dict(path: str, encoder: bool = False) -> Dict[str, torch.Tensor]:
+    """Map a snac 1.2.x SNAC state dict (24 kHz) onto the build's SNAC weight names.
+
+    ``encoder=True`` adds the encoder's ``enc.*`` and the quantiser's ``q{i}.in_proj.*`` keys
+    (``snac_encoder_shapes``); like the decoder's, that mapping follows snac 1.2.x's module tree
+    and is UNVERIFIED until a checkpoint is supplied."""
     if os.path.isdir(path):
         cand = glob.glob(os.path.join(path, "*.safetensors")) + \
             glob.glob(os.path.join(path, "*.bin")) + glob.glob(os.path.join(path, "*.pt"))
@@ -237,6 +283,33 @@ def load_snac_state_dict(path: str) -> Dict[str, torch.Tensor]:
     out["out.conv.w"] = w(d + "7")
     out["out.conv.b"] = sd[d + "7.bias"].float()
     shapes = snac_shapes()
+    if encoder:
+        shapes = {**shapes, **snac_encoder_shapes()}
+        for i in range(3):
+            q = f"quantizer.quantizers.{i}.in_proj"
+            out[f"q{i}.in_proj.w"] = w(q).reshape(8, 768)
+            out[f"q{i}.in_proj.b"] = sd[q + ".bias"].float()
+        e = "encoder.block."
+        out["enc.in.w"] = w(e + "0")
+        out["enc.in.b"] = sd[e + "0.bias"].float()
+        for k in range(4):
+            m = f"{e}{1 + k}.block."
+            p = f"enc.b{k}."
+            c = 48 << k
+            for j in range(3):
+                r = f"{m}{j}.block."
+                q = f"{p}r{j}."
+                out[q + "alpha1"] = sd[r + "0.alpha"].float().reshape(-1)
+                out[q + "dw.w"] = w(r + "1")
+                out[q + "dw.b"] = sd[r + "1.bias"].float()
+                out[q + "alpha2"] = sd[r + "2.alpha"].float().reshape(-1)
+                out[q + "pw.w"] = w(r + "3").reshape(c, c)
+                out[q + "pw.b"] = sd[r + "3.bias"].float()
+            out[p + "alpha"] = sd[m + "3.alpha"].float().reshape(-1)
+            out[p + "down.w"] = w(m + "4")
+            out[p + "down.b"] = sd[m + "4.bias"].float()
+        out["enc.out.dw.w"] = w(e + "5")
+        out["enc.out.dw.b"] = sd[e + "5.bias"].float()
     for k, v in out.items():
         if tuple(v.shape) != shapes[k]:
             raise ValueError(f"SNAC {k}: shape {tuple(v.shape)} != {shapes[k]}")
