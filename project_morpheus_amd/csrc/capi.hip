@@ -2,6 +2,7 @@
 // the decode-step schedule, hipGraph capture/replay, and the SNAC window pipeline.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <algorithm>
@@ -158,7 +159,7 @@ struct mx_llm {
   int legacy_gemv = 0;          // option: grid-stride GEMV for R = 1 too (A/B timing)
   int att_cpw_b1 = 0;           // option: chunks per wave, single-row attention (0 = auto)
   int att_cpw_batch = 0;        // option: same for multi-row (batched decode / prefill); 0 =
-                                // auto (att_cpw_auto): measured -14 % attention at 32 rows
+                                // auto (att_shape): measured -14 % attention at 32 rows
   int att_nw_b1 = 4, att_nw_batch = 8;  // options: attention waves per block (4 or 8; measured)
   int att_b1_short = 1;                 // option: one-row attention may take 64 / 96-position
                                         // splits (2: both, 1: 96 only; 0: from 128). 1 measured
@@ -714,13 +715,26 @@ static void att_batch_shape(const mx_llm* x, int R, int max_len, int* nw, int* c
   *cpw = att_cpw_pick((chunks + splits * *nw - 1) / (splits * *nw), *nw);
 }
 
-static int att_cpw_auto(const mx_llm* x, int R, int max_len) {
-  int nw = 4, cpw = 1;
+// The attention launch of R rows over contexts up to max_len: waves per block, chunks per
+// wave and the split count (grid x) that follows from them.
+// A captured decode step serves every length of its split count, so its grid is sized for
+// nsplit * S positions (S = 32 * nw * cpw) while the shape is chosen from the true length.  The
+// two agree because the shape lists of att_b1_shape and of att_batch_shape's att_nw6 branch are in
+// increasing split size: a length rounded up to nsplit * S still fails every earlier entry and
+// still fits the chosen one.  New entries must keep that order.
+struct AttShape {
+  int nw, cpw, nsplit;
+  int S() const { return 32 * nw * cpw; }  // positions per split
+};
+
+static AttShape att_shape(const mx_llm* x, int R, int max_len) {
+  AttShape s{4, 1, 0};
   if (R == 1)
-    att_b1_shape(x, max_len, &nw, &cpw);
+    att_b1_shape(x, max_len, &s.nw, &s.cpw);
   else
-    att_batch_shape(x, R, max_len, &nw, &cpw);
-  return cpw;
+    att_batch_shape(x, R, max_len, &s.nw, &s.cpw);
+  s.nsplit = (max_len + s.S() - 1) / s.S();
+  return s;
 }
 
 struct RowSet {
@@ -729,11 +743,17 @@ struct RowSet {
   const int32_t* pos;
   int R;
   int max_len;  // upper bound of any row's position + 1 (sizes the attention grid)
-  int cpw;      // attention chunks per wave (att_cpw_auto)
+  int cpw;      // attention chunks per wave (att_shape)
   int nw;       // attention waves per block
   int nsplit;   // attention splits of the launch (grid x)
   bool decode;  // decode rows (one position each, own KV slots), not a prefill's prompt rows
 };
+
+static RowSet row_set(const mx_llm* x, float* h, const int32_t* slot, const int32_t* pos, int R,
+                      int max_len, bool decode) {
+  const AttShape s = att_shape(x, R, max_len);
+  return RowSet{h, slot, pos, R, max_len, s.cpw, s.nw, s.nsplit, decode};
+}
 
 static void attach_ws(mx_llm* x, GemvArgs& g) {
   g.rows_lds_pad = x->rows_lds_pad;
@@ -770,6 +790,81 @@ static void nt_cap(const mx_llm* x, GemvArgs& g, int kind_bit, int R) {
   if (kind_bit < 4 && x->rows_target_k[kind_bit] > 0) g.rows_target = x->rows_target_k[kind_bit];
 }
 
+// ---- GEMV launch arguments: one builder per projection kind ---------------------------
+// Each returns what the kind's launch over R rows carries wherever it is enqueued (the step,
+// the prefills, the probes): weights, fragment-major copy and scales, N / K, strides, norm
+// weight, workspace, tile options.  The callers add X / Y, the row tables and what is theirs
+// alone.  A field no builder or caller sets stays zero: the kernels branch on null pointers.
+static GemvArgs gemv_base(mx_llm* x, int kind_bit, int R, const void* W, const void* Wf,
+                          const float* wscale, int N, int K) {
+  GemvArgs g{};
+  attach_ws(x, g);
+  nt_cap(x, g, kind_bit, R);
+  g.R = R; g.W = W; g.wscale = wscale; g.wdtype = x->c.wdtype; g.N = N; g.K = K; g.xstride = K;
+  if (x->rows_frag) g.Wf = Wf;
+  if (kind_bit < 4) {  // (the lm_head launch carries neither)
+    g.force_legacy = x->legacy_gemv;
+    g.wpb = x->gemv_wpb;
+  }
+  return g;
+}
+
+// QKV + RoPE + KV append of layer li (the caller: X, row_slot, row_pos, attach_qkv_parts)
+static GemvArgs qkv_args(mx_llm* x, int li, int R) {
+  const auto& c = x->c;
+  const LayerW& l = x->L[li];
+  GemvArgs g = gemv_base(x, 0, R, l.wqkv, l.wqkv_f, l.sqkv, (c.heads + 2 * c.kv_heads) * 128, c.hidden);
+  g.eps = c.eps; g.norm_w = l.attn_norm;
+  g.rope_cos = x->rope_cos; g.rope_sin = x->rope_sin;
+  g.kcache = x->kcache + x->kv_layer_elems * li; g.vcache = x->vcache + x->kv_layer_elems * li;
+  g.heads = c.heads; g.kv_heads = c.kv_heads; g.max_pos = c.max_pos; g.Q = x->q;
+  return g;
+}
+
+// Decode rows at >= 2 rows: the qkv GEMM's K ranges store raw partials for the attention
+// launch to sum (no split-K seam), when the option is on and the ranges fit the buffers.
+static bool attach_qkv_parts(const mx_llm* x, GemvArgs& g) {
+  if (g.R < 2 || !x->rows_qkv_parts || x->legacy_gemv || v4::rows_qkv_nkc_v4(g) > mx_llm::qkv_nkc_cap)
+    return false;
+  g.qkv_parts = x->qkv_parts;
+  g.qkv_ss = x->qkv_ss;
+  return true;
+}
+
+// O projection + residual (the caller: X, Y and the attention-merge fields)
+static GemvArgs o_args(mx_llm* x, int li, int R) {
+  const LayerW& l = x->L[li];
+  GemvArgs g = gemv_base(x, 1, R, l.wo, l.wo_f, l.so, x->c.hidden, x->c.heads * 128);
+  g.ystride = x->c.hidden; g.rpw = x->rpw_o;
+  return g;
+}
+
+// gate/up + SiLU*up (the caller: X, Y)
+static GemvArgs gu_args(mx_llm* x, int li, int R) {
+  const LayerW& l = x->L[li];
+  GemvArgs g = gemv_base(x, 2, R, l.wgu, l.wgu_f, l.sgu, 2 * x->c.ffn, x->c.hidden);
+  g.eps = x->c.eps; g.norm_w = l.mlp_norm; g.rpw = x->rpw_gu;
+  return g;
+}
+
+// down + residual (the caller: X, Y)
+static GemvArgs down_args(mx_llm* x, int li, int R) {
+  const LayerW& l = x->L[li];
+  GemvArgs g = gemv_base(x, 3, R, l.wd, l.wd_f, l.sd, x->c.hidden, x->c.ffn);
+  g.ystride = x->c.hidden; g.rpw = x->rpw_down;
+  return g;
+}
+
+// lm_head + penalty + argmax (the caller: X, row_slot, best, logits; the step also row_pos, V,
+// the grammar and the row window)
+static GemvArgs head_args(mx_llm* x, int R) {
+  const auto& c = x->c;
+  GemvArgs g = gemv_base(x, 4, R, x->lm, x->lm_f, x->slm, c.vocab, c.hidden);
+  g.eps = c.eps; g.norm_w = x->norm; g.seen = x->seen; g.penalty = x->penalty;
+  g.samp_temp = x->samp_temp; g.logits_all = x->logits_all;
+  return g;
+}
+
 // Optional per-launch timing (eager runs only): prof->ev[k] brackets launch class k.
 enum { PK_QKV = 0, PK_ATTN, PK_O, PK_GU, PK_DOWN, PK_HEAD, PK_COMMIT, PK_ENGINE, PK_N };
 struct Prof {
@@ -792,27 +887,11 @@ static hipError_t enqueue_layers(mx_llm* x, const RowSet& rs, hipStream_t st, Pr
   const int qkv_rows = QD + 2 * c.kv_heads * 128;
   hipError_t e = hipSuccess;
   for (int li = 0; li < c.layers && e == hipSuccess; ++li) {
-    const LayerW& l = x->L[li];
-    uint16_t* kc = x->kcache + x->kv_layer_elems * li;
-    uint16_t* vc = x->vcache + x->kv_layer_elems * li;
-    GemvArgs g{};
-    attach_ws(x, g);
-    nt_cap(x, g, 0, rs.R);
-    g.R = rs.R;
-    g.eps = c.eps;
     // QKV + RoPE + KV append
-    g.W = l.wqkv; g.wscale = l.sqkv; g.wdtype = c.wdtype; g.N = qkv_rows; g.K = H; g.X = rs.h; g.xstride = H; g.norm_w = l.attn_norm;
-    if (x->rows_frag) g.Wf = l.wqkv_f;
-    g.rope_cos = x->rope_cos; g.rope_sin = x->rope_sin; g.row_slot = rs.slot; g.row_pos = rs.pos;
-    g.kcache = kc; g.vcache = vc; g.heads = c.heads; g.kv_heads = c.kv_heads;
-    g.max_pos = c.max_pos; g.Q = x->q; g.force_legacy = x->legacy_gemv; g.wpb = x->gemv_wpb;
+    GemvArgs g = qkv_args(x, li, rs.R);
+    g.X = rs.h; g.row_slot = rs.slot; g.row_pos = rs.pos;
     // decode at >= 2 rows: the K ranges' raw partials go to the attention launch (no seam)
-    const bool parts = rs.decode && rs.R >= 2 && x->rows_qkv_parts && !x->legacy_gemv &&
-                       v4::rows_qkv_nkc_v4(g) <= mx_llm::qkv_nkc_cap;
-    if (parts) {
-      g.qkv_parts = x->qkv_parts;
-      g.qkv_ss = x->qkv_ss;
-    }
+    const bool parts = rs.decode && attach_qkv_parts(x, g);
     PROF_BEGIN(PK_QKV);
     e = launch_gemv(g, EPI_QKV, true, st);
     PROF_END();
@@ -823,7 +902,7 @@ static hipError_t enqueue_layers(mx_llm* x, const RowSet& rs, hipStream_t st, Pr
       at.qkv_n = qkv_rows; at.hidden = H; at.eps = c.eps;
       at.rope_cos = x->rope_cos; at.rope_sin = x->rope_sin;
     }
-    at.Q = x->q; at.kcache = kc; at.vcache = vc; at.row_slot = rs.slot; at.row_pos = rs.pos;
+    at.Q = x->q; at.kcache = g.kcache; at.vcache = g.vcache; at.row_slot = rs.slot; at.row_pos = rs.pos;
     at.heads = c.heads; at.kv_heads = c.kv_heads; at.max_pos = c.max_pos;
     at.scale = 1.0f / sqrtf(128.0f);
     at.cpw = rs.cpw;
@@ -833,12 +912,8 @@ static hipError_t enqueue_layers(mx_llm* x, const RowSet& rs, hipStream_t st, Pr
     at.split_stride = 32 * rs.nw * rs.cpw < ATT_S_MIN ? c.max_pos / 64 : c.max_pos / ATT_S_MIN;
     // O projection + residual; it merges the attention splits itself (no ticket round trip)
     // at one row, and at 2-16 rows when its tiling allows (option rows_merge)
-    GemvArgs o{};
-    attach_ws(x, o);
-    nt_cap(x, o, 1, rs.R);
-    o.R = rs.R; o.W = l.wo; o.wscale = l.so; o.wdtype = c.wdtype; o.N = H; o.K = QD; o.X = x->att; o.xstride = QD; o.Y = rs.h;
-    o.ystride = H; o.force_legacy = x->legacy_gemv; o.wpb = x->gemv_wpb; o.rpw = x->rpw_o;
-    if (x->rows_frag) o.Wf = l.wo_f;
+    GemvArgs o = o_args(x, li, rs.R);
+    o.X = x->att; o.Y = rs.h;
     o.att_S = 32 * rs.nw * rs.cpw; o.att_stride = at.split_stride; o.att_nsm = rs.nsplit;
     o.heads = c.heads; o.kv_heads = c.kv_heads; o.row_pos = rs.pos;
     const bool b1_merge = rs.R == 1 && !x->legacy_gemv && x->o_merge && rs.nsplit <= 8;
@@ -861,23 +936,15 @@ static hipError_t enqueue_layers(mx_llm* x, const RowSet& rs, hipStream_t st, Pr
     PROF_END();
     if (e != hipSuccess) break;
     // gate/up + SiLU*up
-    GemvArgs gu{};
-    attach_ws(x, gu);
-    nt_cap(x, gu, 2, rs.R);
-    gu.R = rs.R; gu.eps = c.eps; gu.W = l.wgu; gu.wscale = l.sgu; gu.wdtype = c.wdtype; gu.N = 2 * c.ffn; gu.K = H; gu.X = rs.h;
-    gu.xstride = H; gu.norm_w = l.mlp_norm; gu.Y = x->act; gu.force_legacy = x->legacy_gemv; gu.wpb = x->gemv_wpb; gu.rpw = x->rpw_gu;
-    if (x->rows_frag) gu.Wf = l.wgu_f;
+    GemvArgs gu = gu_args(x, li, rs.R);
+    gu.X = rs.h; gu.Y = x->act;
     PROF_BEGIN(PK_GU);
     e = launch_gemv(gu, EPI_SILU, true, st);
     PROF_END();
     if (e != hipSuccess) break;
     // down + residual
-    GemvArgs d{};
-    attach_ws(x, d);
-    nt_cap(x, d, 3, rs.R);
-    d.R = rs.R; d.W = l.wd; d.wscale = l.sd; d.wdtype = c.wdtype; d.N = H; d.K = c.ffn; d.X = x->act; d.xstride = c.ffn; d.Y = rs.h;
-    d.ystride = H; d.force_legacy = x->legacy_gemv; d.wpb = x->gemv_wpb; d.rpw = x->rpw_down;
-    if (x->rows_frag) d.Wf = l.wd_f;
+    GemvArgs d = down_args(x, li, rs.R);
+    d.X = x->act; d.Y = rs.h;
     PROF_BEGIN(PK_DOWN);
     e = launch_gemv(d, EPI_RESID, false, st);
     PROF_END();
@@ -921,13 +988,8 @@ static hipError_t enqueue_head_at(mx_llm* x, const float* h, const int32_t* slot
                                   const int32_t* pos, int R, unsigned long long* best, float* lg,
                                   int sampler, bool window, hipStream_t st) {
   const auto& c = x->c;
-  GemvArgs g{};
-  attach_ws(x, g);
-  nt_cap(x, g, 4, R);
-  g.R = R; g.eps = c.eps; g.W = x->lm; g.Wf = x->rows_frag ? x->lm_f : nullptr; g.wscale = x->slm; g.wdtype = c.wdtype; g.N = c.vocab; g.K = c.hidden; g.X = h;
-  g.xstride = c.hidden; g.norm_w = x->norm; g.row_slot = slot; g.seen = x->seen;
-  g.penalty = x->penalty; g.samp_temp = x->samp_temp; g.best = best;
-  g.logits = lg; g.logits_all = x->logits_all;
+  GemvArgs g = head_args(x, R);
+  g.X = h; g.row_slot = slot; g.best = best; g.logits = lg;
   g.V = c.vocab; g.row_pos = pos; g.gram = grammar_args(x);
   if (window) {
     // row-major weights and scales by pointer; the fragment-major copy by tile offset
@@ -955,15 +1017,6 @@ static int decode_max_len(const mx_llm* x, int n_rows) {
   for (int r = 0; r < n_rows; ++r)
     if (x->row_active[r]) m = std::max(m, x->pos_mirror[r] + 1);
   return m;
-}
-
-static int att_nw_of(const mx_llm* x, int R, int max_len) {
-  int nw = 4, cpw = 1;
-  if (R == 1)
-    att_b1_shape(x, max_len, &nw, &cpw);
-  else
-    att_batch_shape(x, R, max_len, &nw, &cpw);
-  return nw;
 }
 
 // A step runs the lm_head over the grammar's row window when every active row is constrained
@@ -1007,19 +1060,27 @@ static EngineArgs engine_args(const mx_llm* x) {
   return a;
 }
 
-static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, int sampler,
-                                 bool window, hipStream_t st, Prof* prof) {
+// The fields every commit launch shares; the callers set best, the row pointers, h, dst_row
+// and abort_word.
+static CommitArgs commit_args(const mx_llm* x) {
   const auto& c = x->c;
+  CommitArgs cm{};
+  cm.seen = x->seen; cm.hist = x->hist_dev; cm.embed = x->embed; cm.hidden = c.hidden;
+  cm.vocab = c.vocab; cm.max_pos = c.max_pos; cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
+  cm.last_n = x->last_n; cm.recent = x->recent;
+  return cm;
+}
+
+// One decode step over rs's rows (the attention shape is the caller's: mx_llm_decode).
+static hipError_t enqueue_decode(mx_llm* x, const RowSet& rs, int sampler, bool window,
+                                 hipStream_t st, Prof* prof) {
+  const int n_rows = rs.R;
   hipError_t e = hipSuccess;
   if (n_rows == 1 && x->b1_engine) {  // every layer in one persistent launch
     PROF_BEGIN(PK_ENGINE);
     e = launch_engine_b1(engine_args(x), x->engine_grid, st);
     PROF_END();
   } else {
-    const int nw = att_nw_of(x, n_rows, max_len);
-    const int S = 32 * nw * cpw;
-    RowSet rs{x->h_dec, x->row_slot, x->row_pos, n_rows, max_len, cpw, nw,
-              (max_len + S - 1) / S, true};
     e = enqueue_layers(x, rs, st, prof);
   }
   PROF_BEGIN(PK_HEAD);
@@ -1028,12 +1089,9 @@ static hipError_t enqueue_decode(mx_llm* x, int n_rows, int max_len, int cpw, in
   PROF_END();
   PROF_BEGIN(PK_COMMIT);
   if (e == hipSuccess) {
-    CommitArgs cm{};
+    CommitArgs cm = commit_args(x);
     cm.best = x->best; cm.row_slot = x->row_slot; cm.row_pos = x->row_pos;
-    cm.row_token = x->row_token; cm.seen = x->seen; cm.hist = x->hist_dev; cm.embed = x->embed;
-    cm.h = x->h_dec; cm.hidden = c.hidden; cm.vocab = c.vocab; cm.max_pos = c.max_pos;
-    cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
-    cm.last_n = x->last_n; cm.recent = x->recent;
+    cm.row_token = x->row_token; cm.h = x->h_dec;
     // an engine launch that gave up commits nothing (its history entry reads -1)
     cm.abort_word = (n_rows == 1 && x->b1_engine) ? x->eng_status_d : nullptr;
     e = launch_commit(cm, n_rows, st);
@@ -1055,6 +1113,111 @@ static int row_of_slot(const mx_llm* x, int slot) {
   return -1;
 }
 
+// ---- what the prefill entry points share -----------------------------------------------
+// The refusal of a request's sampling parameters, or null.
+static const char* check_sampling(const mx_sampling& sp, const mx_sampling_ext& xe) {
+  if (!(sp.repetition_penalty > 0.f) || !(sp.top_p > 0.f) || sp.temperature < 0.f)
+    return "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0";
+  if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
+      xe.penalty_last_n >= PEN_RING)
+    return "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255";
+  return nullptr;
+}
+
+static bool ids_in_vocab(const mx_llm* x, const int32_t* ids, int n) {
+  for (int i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= x->c.vocab) return false;
+  return true;
+}
+
+// The sampler node a stream with these parameters needs.
+static int sampler_kind(const mx_sampling& sp, const mx_sampling_ext& xe) {
+  if (!(sp.temperature > 0.f)) return SMP_NONE;
+  return xe.top_k > 0 || xe.min_p > 0.f ? SMP_CHAIN : SMP_PLAIN;
+}
+
+// Host mirror of a decode row bound to `slot`, its next token at position `pos`.
+static void bind_row(mx_llm* x, int row, int slot, int pos, int sampler, int origin) {
+  x->pos_mirror[row] = pos;
+  x->row_active[row] = 1;
+  x->row_samples[row] = sampler != SMP_NONE ? 1 : 0;
+  x->row_chain[row] = sampler == SMP_CHAIN ? 1 : 0;
+  x->row_origin[row] = origin;
+  x->row_slot_h[row] = slot;
+}
+
+// One prompt span: n ids onto `slot` behind the pos0 positions it holds.  The rows carry
+// pos = pos0 + i; the attention grid is sized by max_len = pos0 + n (behind a history: prompt
+// rows attending over more positions than there are rows, i.e. the multi-row kernel with the
+// split counts decode rows reach, the one-row kernels for a one-id span).  A span that is not
+// the prompt's last runs the layers and appends K / V, nothing else.  The last one builds the
+// slot's penalty state over the whole prompt [0, pos0 + n), sets the grammar origin to
+// pos0 + n, runs head, sampler and commit on its last row and binds `row`.  A whole prompt
+// (pos0 = 0, last) has its ids in pre_ids, and embed_rows marks them seen on the way; behind a
+// history the id history (the host mirror) is uploaded once to cont_ids and marked behind the
+// layers.  The callers have made every refusal: from here on only the runtime can fail.
+static int prefill_span(mx_llm* x, int slot, int row, const int32_t* ids, int n, int pos0,
+                        bool last, const mx_sampling& sp, const mx_sampling_ext& xe,
+                        hipStream_t st) {
+  const auto& c = x->c;
+  const int max_len = pos0 + n, win = xe.penalty_last_n;
+  const bool hist = last && pos0 != 0;  // the prompt's earlier ids are needed again
+  MX_TRY(x, hipSetDevice(x->device));
+  if (hist && !x->cont_ids) MX_TRY(x, x->alloc(&x->cont_ids, (size_t)c.max_pos));
+  if (last) {
+    MX_TRY(x, launch_set_slot_params(x->penalty, x->samp_temp, x->samp_top_p, x->samp_seed, slot,
+                                     sp.repetition_penalty, sp.temperature,
+                                     sp.top_p < 1.f ? sp.top_p : 1.f, sp.seed, st));
+    // every prefill starts the slot clean: seen flags / window counts here, the ring below
+    MX_TRY(x, hipMemsetAsync(x->seen + (size_t)slot * c.vocab, 0, c.vocab, st));
+  }
+  int32_t* dev_ids = x->pre_ids;  // the span's ids on the device
+  if (hist) {  // the slot's history [0, pos0) and the span's ids behind it, one contiguous copy
+    MX_TRY(x, hipMemcpyAsync(x->cont_ids, x->slot_ids.data() + (size_t)slot * c.max_pos,
+                             (size_t)pos0 * 4, hipMemcpyHostToDevice, st));
+    dev_ids = x->cont_ids + pos0;
+  }
+  MX_TRY(x, hipMemcpyAsync(dev_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  MX_TRY(x, launch_set_rows(x->pre_slot, x->pre_pos, n, slot, pos0, st));
+  // (seen marks here only for a whole prompt without a window; otherwise behind the layers)
+  MX_TRY(x, launch_embed_rows(dev_ids, n, slot, x->embed, c.hidden, c.vocab,
+                              last && pos0 == 0 && win == 0 ? x->seen : nullptr, x->h_pre, st));
+  MX_TRY(x, enqueue_layers(x, row_set(x, x->h_pre, x->pre_slot, x->pre_pos, n, max_len, false),
+                           st, nullptr));
+  if (!last) {
+    record_prompt(x, slot, pos0, ids, n);
+    return MX_OK;
+  }
+  // the extras, the ring and (window mode: the bytes are counts, filled serially, since
+  // embed_rows marks from many blocks) the window are first read by the head and the commit:
+  // set behind the layers, the launches in front of them are the same with and without extras
+  MX_TRY(x, launch_set_slot_ext(x->samp_top_k, x->samp_min_p, x->last_n, slot, xe.top_k,
+                                xe.min_p, win, st));
+  MX_TRY(x, hipMemsetAsync(x->recent + (size_t)slot * PEN_RING, 0, PEN_RING * 4, st));
+  const int32_t* all_ids = dev_ids - pos0;  // the whole prompt [0, max_len)
+  if (win > 0)  // its last N positions: they may straddle a seam
+    MX_TRY(x, launch_window_prefill(all_ids, max_len, win, slot, c.vocab, x->seen, x->recent, st));
+  else if (pos0 != 0)
+    MX_TRY(x, launch_mark_seen(all_ids, max_len, slot, c.vocab, x->seen, st));
+  // a constrained slot counts its phases from the prompt's end (-1: unconstrained)
+  const int origin = x->gram_on && x->slot_grammar[slot] ? max_len : -1;
+  if (x->gram_on) MX_TRY(x, launch_set_slot_origin(x->gram_origin, slot, origin, st));
+  MX_TRY(x, hipMemsetAsync(x->best + row, 0, 8, st));
+  const int sampler = sampler_kind(sp, xe);
+  MX_TRY(x, enqueue_head(x, x->h_pre + (size_t)(n - 1) * c.hidden, x->pre_slot + (n - 1),
+                         x->pre_pos + (n - 1), 1, x->best + row, sampler,
+                         origin >= 0 && x->grammar_head && x->win_n > 0, st));
+  // bind decode row -> slot at the prompt's last position, then commit (advances to pos0 + n)
+  MX_TRY(x, launch_set_rows(x->row_slot + row, x->row_pos + row, 1, slot, max_len - 1, st));
+  CommitArgs cm = commit_args(x);
+  cm.best = x->best + row; cm.row_slot = x->row_slot + row; cm.row_pos = x->row_pos + row;
+  cm.row_token = x->row_token + row; cm.h = x->h_dec + (size_t)row * c.hidden;
+  MX_TRY(x, launch_commit(cm, 1, st));
+  bind_row(x, row, slot, max_len, sampler, origin);
+  record_prompt(x, slot, pos0, ids, n);
+  return MX_OK;
+}
+
 extern "C" int mx_llm_prefill(mx_llm* x, int slot, int row, const int32_t* ids, int n,
                               const mx_sampling* sp, void* stream) {
   return mx_llm_prefill_ex(x, slot, row, ids, n, sp, nullptr, stream);
@@ -1064,72 +1227,16 @@ extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* id
                                  const mx_sampling* sp, const mx_sampling_ext* ext,
                                  void* stream) {
   if (!x || !ids || !sp) return MX_ERR_ARG;
-  if (!(sp->repetition_penalty > 0.f) || !(sp->top_p > 0.f) || sp->temperature < 0.f)
-    MX_FAIL(x, MX_ERR_ARG, "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0");
   const mx_sampling_ext neutral{0, 0.f, 0};
   const mx_sampling_ext& xe = ext ? *ext : neutral;
-  if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
-      xe.penalty_last_n >= PEN_RING)
-    MX_FAIL(x, MX_ERR_ARG,
-            "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255");
+  if (const char* m = check_sampling(*sp, xe)) MX_FAIL(x, MX_ERR_ARG, m);
   if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
   const auto& c = x->c;
   if (slot < 0 || slot >= c.max_slots || row < 0 || row >= c.max_batch)
     MX_FAIL(x, MX_ERR_ARG, "slot/row out of range");
   if (n < 1 || n > c.max_prefill || n >= c.max_pos) MX_FAIL(x, MX_ERR_ARG, "bad prompt length");
-  for (int i = 0; i < n; ++i)
-    if (ids[i] < 0 || ids[i] >= c.vocab) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
-  hipStream_t st = (hipStream_t)stream;
-  MX_TRY(x, hipSetDevice(x->device));
-  MX_TRY(x, launch_set_slot_params(x->penalty, x->samp_temp, x->samp_top_p, x->samp_seed, slot,
-                                   sp->repetition_penalty, sp->temperature,
-                                   sp->top_p < 1.f ? sp->top_p : 1.f, sp->seed, st));
-  const int win = xe.penalty_last_n;
-  // every prefill starts the slot clean: seen flags / window counts here, the ring below
-  MX_TRY(x, hipMemsetAsync(x->seen + (size_t)slot * c.vocab, 0, c.vocab, st));
-  MX_TRY(x, hipMemcpyAsync(x->pre_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  MX_TRY(x, launch_set_rows(x->pre_slot, x->pre_pos, n, slot, 0, st));
-  MX_TRY(x, launch_embed_rows(x->pre_ids, n, slot, x->embed, c.hidden, c.vocab,
-                              win > 0 ? nullptr : x->seen, x->h_pre, st));
-  RowSet rs{x->h_pre, x->pre_slot, x->pre_pos, n, n, att_cpw_auto(x, n, n),
-            att_nw_of(x, n, n), 0, false};
-  rs.nsplit = (n + 32 * rs.nw * rs.cpw - 1) / (32 * rs.nw * rs.cpw);
-  MX_TRY(x, enqueue_layers(x, rs, st, nullptr));
-  // the extras, the ring and (window mode: the bytes are counts, filled serially, since
-  // embed_rows marks from many blocks) the window are first read by the head and the commit:
-  // set behind the layers, the launches in front of them are the same with and without extras
-  MX_TRY(x, launch_set_slot_ext(x->samp_top_k, x->samp_min_p, x->last_n, slot, xe.top_k,
-                                xe.min_p, win, st));
-  MX_TRY(x, hipMemsetAsync(x->recent + (size_t)slot * PEN_RING, 0, PEN_RING * 4, st));
-  if (win > 0)
-    MX_TRY(x, launch_window_prefill(x->pre_ids, n, win, slot, c.vocab, x->seen, x->recent, st));
-  // a constrained slot counts its phases from the prompt's end (-1: unconstrained)
-  const int origin = x->gram_on && x->slot_grammar[slot] ? n : -1;
-  if (x->gram_on) MX_TRY(x, launch_set_slot_origin(x->gram_origin, slot, origin, st));
-  MX_TRY(x, hipMemsetAsync(x->best + row, 0, 8, st));
-  const bool samples = sp->temperature > 0.f;
-  const bool chain = samples && (xe.top_k > 0 || xe.min_p > 0.f);
-  MX_TRY(x, enqueue_head(x, x->h_pre + (size_t)(n - 1) * c.hidden, x->pre_slot + (n - 1),
-                         x->pre_pos + (n - 1), 1, x->best + row,
-                         chain ? SMP_CHAIN : samples ? SMP_PLAIN : SMP_NONE,
-                         origin >= 0 && x->grammar_head && x->win_n > 0, st));
-  // bind decode row -> slot at position n-1, then commit (advances to n)
-  MX_TRY(x, launch_set_rows(x->row_slot + row, x->row_pos + row, 1, slot, n - 1, st));
-  CommitArgs cm{};
-  cm.best = x->best + row; cm.row_slot = x->row_slot + row; cm.row_pos = x->row_pos + row;
-  cm.row_token = x->row_token + row; cm.seen = x->seen; cm.hist = x->hist_dev;
-  cm.embed = x->embed; cm.h = x->h_dec + (size_t)row * c.hidden; cm.hidden = c.hidden;
-  cm.vocab = c.vocab; cm.max_pos = c.max_pos; cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
-  cm.last_n = x->last_n; cm.recent = x->recent;
-  MX_TRY(x, launch_commit(cm, 1, st));
-  x->pos_mirror[row] = n;
-  x->row_active[row] = 1;
-  x->row_samples[row] = samples ? 1 : 0;
-  x->row_chain[row] = chain ? 1 : 0;
-  x->row_origin[row] = origin;
-  record_prompt(x, slot, 0, ids, n);
-  x->row_slot_h[row] = slot;
-  return MX_OK;
+  if (!ids_in_vocab(x, ids, n)) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
+  return prefill_span(x, slot, row, ids, n, 0, true, *sp, xe, (hipStream_t)stream);
 }
 
 // Packed prefill: the segments' prompt rows as ONE row set through the layers (each row
@@ -1151,15 +1258,8 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
   bool any_window = false, all_constrained = x->gram_on;
   for (int s = 0; s < n_segs; ++s) {
     const mx_prefill_seg& g = segs[s];
-    const mx_sampling& sp = g.params;
-    const mx_sampling_ext& xe = g.ext;
     if (!g.ids_host) MX_FAIL(x, MX_ERR_ARG, "segment without ids");
-    if (!(sp.repetition_penalty > 0.f) || !(sp.top_p > 0.f) || sp.temperature < 0.f)
-      MX_FAIL(x, MX_ERR_ARG, "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0");
-    if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
-        xe.penalty_last_n >= PEN_RING)
-      MX_FAIL(x, MX_ERR_ARG,
-              "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255");
+    if (const char* m = check_sampling(g.params, g.ext)) MX_FAIL(x, MX_ERR_ARG, m);
     if (g.slot < 0 || g.slot >= c.max_slots || g.row < 0 || g.row >= c.max_batch)
       MX_FAIL(x, MX_ERR_ARG, "slot/row out of range");
     if (slot_used[g.slot] || row_used[g.row])
@@ -1168,13 +1268,10 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
     if (g.n_ids < 1 || g.n_ids >= c.max_pos) MX_FAIL(x, MX_ERR_ARG, "bad prompt length");
     R64 += g.n_ids;
     if (R64 > c.max_prefill) MX_FAIL(x, MX_ERR_ARG, "prompts exceed max_prefill rows");
-    for (int i = 0; i < g.n_ids; ++i)
-      if (g.ids_host[i] < 0 || g.ids_host[i] >= c.vocab)
-        MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
+    if (!ids_in_vocab(x, g.ids_host, g.n_ids)) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
     max_n = std::max(max_n, g.n_ids);
-    if (sp.temperature > 0.f)
-      sampler = std::max(sampler, (xe.top_k > 0 || xe.min_p > 0.f) ? (int)SMP_CHAIN : (int)SMP_PLAIN);
-    any_window = any_window || xe.penalty_last_n > 0;
+    sampler = std::max(sampler, sampler_kind(g.params, g.ext));
+    any_window = any_window || g.ext.penalty_last_n > 0;
     all_constrained = all_constrained && x->slot_grammar[g.slot];
   }
   const int R = (int)R64;
@@ -1207,7 +1304,7 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
   }
   const PackSeg* dsegs = reinterpret_cast<const PackSeg*>(x->pk_tab);
   const PackRow* drows = reinterpret_cast<const PackRow*>(x->pk_tab + seg_words);
-  // (pageable source, as mx_llm_prefill_ex's copy of the caller's ids: the runtime has read it
+  // (pageable source, as prefill_span's copy of the caller's ids: the runtime has read it
   // when the call returns, so the next call may rebuild the table)
   MX_TRY(x, hipMemcpyAsync(x->pk_tab, x->pk_host.data(), x->pk_host.size() * 4,
                            hipMemcpyHostToDevice, st));
@@ -1221,10 +1318,8 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
   ps.origin = x->gram_on ? x->gram_origin : nullptr;
   MX_TRY(x, launch_pack_setup(ps, st));
   // the attention grid is sized by the longest segment; shorter rows leave its later splits
-  RowSet rs{x->h_pre, x->pre_slot, x->pre_pos, R, max_n, att_cpw_auto(x, R, max_n),
-            att_nw_of(x, R, max_n), 0, false};
-  rs.nsplit = (max_n + 32 * rs.nw * rs.cpw - 1) / (32 * rs.nw * rs.cpw);
-  MX_TRY(x, enqueue_layers(x, rs, st, nullptr));
+  MX_TRY(x, enqueue_layers(x, row_set(x, x->h_pre, x->pre_slot, x->pre_pos, R, max_n, false),
+                           st, nullptr));
   if (any_window)
     MX_TRY(x, launch_pack_window(drows, dsegs, n_segs, c.vocab, x->seen, x->recent, st));
   int32_t *hslot = x->pk_idx, *hpos = x->pk_idx + c.max_batch, *hrow = x->pk_idx + 2 * c.max_batch;
@@ -1239,35 +1334,21 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
                             window, st));
   if (x->logits_all || sampler != SMP_NONE)
     MX_TRY(x, launch_pack_logits(x->logits, x->pk_logits, hrow, n_segs, c.vocab, st));
-  CommitArgs cm{};
+  CommitArgs cm = commit_args(x);
   cm.best = x->pk_best; cm.dst_row = hrow; cm.row_slot = x->row_slot; cm.row_pos = x->row_pos;
-  cm.row_token = x->row_token; cm.seen = x->seen; cm.hist = x->hist_dev; cm.embed = x->embed;
-  cm.h = x->h_dec; cm.hidden = c.hidden; cm.vocab = c.vocab; cm.max_pos = c.max_pos;
-  cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
-  cm.last_n = x->last_n; cm.recent = x->recent;
+  cm.row_token = x->row_token; cm.h = x->h_dec;
   MX_TRY(x, launch_commit(cm, n_segs, st));
   for (int s = 0; s < n_segs; ++s) {
     const mx_prefill_seg& g = segs[s];
-    const bool samples = g.params.temperature > 0.f;
-    x->pos_mirror[g.row] = g.n_ids;
-    x->row_active[g.row] = 1;
-    x->row_samples[g.row] = samples ? 1 : 0;
-    x->row_chain[g.row] = samples && (g.ext.top_k > 0 || g.ext.min_p > 0.f) ? 1 : 0;
-    x->row_origin[g.row] = hs[s].origin;
+    bind_row(x, g.row, g.slot, g.n_ids, sampler_kind(g.params, g.ext), hs[s].origin);
     record_prompt(x, g.slot, 0, g.ids_host, g.n_ids);
-    x->row_slot_h[g.row] = g.slot;
   }
   return MX_OK;
 }
 
-// Prompt continuation: a chunk of a prompt behind the pos0 positions its slot already holds.
-// The rows carry pos = pos0 + i; the attention grid is sized by max_len = pos0 + n (prompt rows
-// attending over more positions than there are rows: the multi-row kernel with the split counts
-// decode rows reach, the one-row kernels for a one-id chunk).  A non-final chunk runs the layers
-// and appends K / V, nothing else.  The final chunk builds the slot's penalty state from the id
-// history over [0, pos0 + n) (the host mirror, uploaded once), sets the grammar origin to
-// pos0 + n and runs head, sampler and commit on its last row as mx_llm_prefill_ex does for n.
-// pos0 = 0 with last = 1 IS mx_llm_prefill_ex (the same launches).
+// Prompt continuation: a chunk of a prompt behind the pos0 positions its slot already holds
+// (prefill_span).  pos0 = 0 with last = 1 IS mx_llm_prefill_ex: the same launches, and the same
+// refusals, so the state checks below (which mx_llm_prefill_ex does not make) leave it out.
 extern "C" int mx_llm_prefill_chunk(mx_llm* x, const mx_prefill_chunk* ck, void* stream) {
   if (!x || !ck) return MX_ERR_ARG;
   if (!ck->ids_host) MX_FAIL(x, MX_ERR_ARG, "chunk without ids");
@@ -1282,95 +1363,24 @@ extern "C" int mx_llm_prefill_chunk(mx_llm* x, const mx_prefill_chunk* ck, void*
   if (n < 1 || n > c.max_prefill) MX_FAIL(x, MX_ERR_ARG, "bad chunk length");
   if (pos0 < 0 || (long long)pos0 + n >= c.max_pos)
     MX_FAIL(x, MX_ERR_ARG, "chunk does not fit max_pos");
-  for (int i = 0; i < n; ++i)
-    if (ids[i] < 0 || ids[i] >= c.vocab) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
-  const mx_sampling& sp = ck->params;
-  const mx_sampling_ext& xe = ck->ext;
-  if (last) {
-    if (!(sp.repetition_penalty > 0.f) || !(sp.top_p > 0.f) || sp.temperature < 0.f)
-      MX_FAIL(x, MX_ERR_ARG, "sampling: need repetition_penalty > 0, top_p > 0, temperature >= 0");
-    if (xe.top_k < 0 || !(xe.min_p >= 0.f && xe.min_p <= 1.f) || xe.penalty_last_n < 0 ||
-        xe.penalty_last_n >= PEN_RING)
-      MX_FAIL(x, MX_ERR_ARG,
-              "sampling: need top_k >= 0, 0 <= min_p <= 1, 0 <= penalty_last_n <= 255");
+  if (!ids_in_vocab(x, ids, n)) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
+  if (last)
+    if (const char* m = check_sampling(ck->params, ck->ext)) MX_FAIL(x, MX_ERR_ARG, m);
+  if (!(pos0 == 0 && last)) {
+    // (pos0 = 0 starts the slot over, as every prefill does)
+    if (pos0 != 0 && pos0 != x->slot_len[slot])
+      MX_FAIL(x, MX_ERR_STATE, "chunk at position " + std::to_string(pos0) + ": the slot holds " +
+                                   std::to_string(x->slot_len[slot]));
+    if (row_of_slot(x, slot) >= 0)
+      MX_FAIL(x, MX_ERR_STATE, "chunk onto a slot bound to an active row");
+    // the launch's own argument checks (launch_attention), made before anything is enqueued: the
+    // split count one launch may merge, and the partial slots a (row, kv head) has
+    const AttShape sh = att_shape(x, n, pos0 + n);
+    const int stride = sh.S() < ATT_S_MIN ? c.max_pos / 64 : c.max_pos / ATT_S_MIN;
+    if (sh.nsplit > ATT_MAX_SPLITS || (c.max_pos + sh.S() - 1) / sh.S() > stride)
+      MX_FAIL(x, MX_ERR_ARG, "chunk: the context needs more attention splits than one launch merges");
   }
-  if (pos0 == 0 && last)
-    return mx_llm_prefill_ex(x, slot, row, ids, n, &sp, &xe, stream);
-  // (pos0 = 0 starts the slot over, as every prefill does)
-  if (pos0 != 0 && pos0 != x->slot_len[slot])
-    MX_FAIL(x, MX_ERR_STATE, "chunk at position " + std::to_string(pos0) + ": the slot holds " +
-                                 std::to_string(x->slot_len[slot]));
-  if (row_of_slot(x, slot) >= 0)
-    MX_FAIL(x, MX_ERR_STATE, "chunk onto a slot bound to an active row");
-  const int max_len = pos0 + n;
-  RowSet rs{x->h_pre, x->pre_slot, x->pre_pos, n, max_len, att_cpw_auto(x, n, max_len),
-            att_nw_of(x, n, max_len), 0, false};
-  const int S = 32 * rs.nw * rs.cpw;
-  rs.nsplit = (max_len + S - 1) / S;
-  // the launch's own argument checks (launch_attention), made before anything is enqueued: the
-  // split count one launch may merge, and the partial slots a (row, kv head) has
-  const int stride = S < ATT_S_MIN ? c.max_pos / 64 : c.max_pos / ATT_S_MIN;
-  if (rs.nsplit > ATT_MAX_SPLITS || (c.max_pos + S - 1) / S > stride)
-    MX_FAIL(x, MX_ERR_ARG, "chunk: the context needs more attention splits than one launch merges");
-  hipStream_t st = (hipStream_t)stream;
-  MX_TRY(x, hipSetDevice(x->device));
-  const int32_t* dev_ids = x->pre_ids;
-  if (last) {
-    // the slot's history [0, pos0) and the chunk's ids behind it, one contiguous device copy
-    if (!x->cont_ids) MX_TRY(x, x->alloc(&x->cont_ids, (size_t)c.max_pos));
-    MX_TRY(x, launch_set_slot_params(x->penalty, x->samp_temp, x->samp_top_p, x->samp_seed, slot,
-                                     sp.repetition_penalty, sp.temperature,
-                                     sp.top_p < 1.f ? sp.top_p : 1.f, sp.seed, st));
-    MX_TRY(x, hipMemsetAsync(x->seen + (size_t)slot * c.vocab, 0, c.vocab, st));
-    MX_TRY(x, hipMemcpyAsync(x->cont_ids, x->slot_ids.data() + (size_t)slot * c.max_pos,
-                             (size_t)pos0 * 4, hipMemcpyHostToDevice, st));
-    MX_TRY(x, hipMemcpyAsync(x->cont_ids + pos0, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    dev_ids = x->cont_ids + pos0;
-  } else {
-    MX_TRY(x, hipMemcpyAsync(x->pre_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  }
-  MX_TRY(x, launch_set_rows(x->pre_slot, x->pre_pos, n, slot, pos0, st));
-  // (no seen marks here: the final chunk marks the whole history behind the layers)
-  MX_TRY(x, launch_embed_rows(dev_ids, n, slot, x->embed, c.hidden, c.vocab, nullptr, x->h_pre, st));
-  MX_TRY(x, enqueue_layers(x, rs, st, nullptr));
-  if (!last) {
-    record_prompt(x, slot, pos0, ids, n);
-    return MX_OK;
-  }
-  const int win = xe.penalty_last_n;
-  MX_TRY(x, launch_set_slot_ext(x->samp_top_k, x->samp_min_p, x->last_n, slot, xe.top_k,
-                                xe.min_p, win, st));
-  MX_TRY(x, hipMemsetAsync(x->recent + (size_t)slot * PEN_RING, 0, PEN_RING * 4, st));
-  if (win > 0)  // the last N positions of the whole prompt: they may straddle the seam
-    MX_TRY(x, launch_window_prefill(x->cont_ids, max_len, win, slot, c.vocab, x->seen, x->recent, st));
-  else
-    MX_TRY(x, launch_mark_seen(x->cont_ids, max_len, slot, c.vocab, x->seen, st));
-  const int origin = x->gram_on && x->slot_grammar[slot] ? max_len : -1;
-  if (x->gram_on) MX_TRY(x, launch_set_slot_origin(x->gram_origin, slot, origin, st));
-  MX_TRY(x, hipMemsetAsync(x->best + row, 0, 8, st));
-  const bool samples = sp.temperature > 0.f;
-  const bool chain = samples && (xe.top_k > 0 || xe.min_p > 0.f);
-  MX_TRY(x, enqueue_head(x, x->h_pre + (size_t)(n - 1) * c.hidden, x->pre_slot + (n - 1),
-                         x->pre_pos + (n - 1), 1, x->best + row,
-                         chain ? SMP_CHAIN : samples ? SMP_PLAIN : SMP_NONE,
-                         origin >= 0 && x->grammar_head && x->win_n > 0, st));
-  // bind decode row -> slot at the prompt's last position, then commit (advances to pos0 + n)
-  MX_TRY(x, launch_set_rows(x->row_slot + row, x->row_pos + row, 1, slot, max_len - 1, st));
-  CommitArgs cm{};
-  cm.best = x->best + row; cm.row_slot = x->row_slot + row; cm.row_pos = x->row_pos + row;
-  cm.row_token = x->row_token + row; cm.seen = x->seen; cm.hist = x->hist_dev;
-  cm.embed = x->embed; cm.h = x->h_dec + (size_t)row * c.hidden; cm.hidden = c.hidden;
-  cm.vocab = c.vocab; cm.max_pos = c.max_pos; cm.pos_advance = 1; cm.scratch_slot = c.max_slots;
-  cm.last_n = x->last_n; cm.recent = x->recent;
-  MX_TRY(x, launch_commit(cm, 1, st));
-  x->pos_mirror[row] = max_len;
-  x->row_active[row] = 1;
-  x->row_samples[row] = samples ? 1 : 0;
-  x->row_chain[row] = chain ? 1 : 0;
-  x->row_origin[row] = origin;
-  record_prompt(x, slot, pos0, ids, n);
-  x->row_slot_h[row] = slot;
-  return MX_OK;
+  return prefill_span(x, slot, row, ids, n, pos0, last, ck->params, ck->ext, (hipStream_t)stream);
 }
 
 // dst holds src's first n_pos positions afterwards: K / V of every layer (one kv_fork_kernel
@@ -1454,23 +1464,25 @@ extern "C" int mx_llm_decode(mx_llm* x, int n_rows, void* stream) {
   if (engine_gave_up(x, st)) return MX_ERR_HIP;
   // one graph per (row count, attention split count): kernels read positions from device
   // memory; the split count only sizes the attention grid (the engine sizes its own)
-  const bool engine = n_rows == 1 && x->b1_engine;
-  const int ml = decode_max_len(x, n_rows);
-  const int cpw = engine ? 1 : att_cpw_auto(x, n_rows, ml);
-  const int nw = engine ? 1 : att_nw_of(x, n_rows, ml);
-  const int S = 32 * cpw * nw;
-  const int nsplit = engine ? 0 : (ml + S - 1) / S;
+  // the shape comes from the true length, once; the captured launch is sized for every length
+  // of its split count (att_shape)
+  RowSet rs = row_set(x, x->h_dec, x->row_slot, x->row_pos, n_rows, decode_max_len(x, n_rows), true);
+  if (n_rows == 1 && x->b1_engine) {
+    rs.cpw = rs.nw = 1;
+    rs.nsplit = 0;
+  }
+  rs.max_len = rs.nsplit * 32 * rs.nw * rs.cpw;
   // (chunks and waves are part of the key: one nsplit can come from several shapes; so is
   // the sampler node: all-greedy graphs have none, the others sample_kernel or the chain)
   // ... and whether the lm_head runs over the grammar's row window
   const int sampler = sampler_of(x, n_rows);
   const bool window = window_of(x, n_rows);
-  const int key = ((((n_rows * 16 + cpw) * 16 + nw) * 4096 + nsplit) * 4 + sampler) * 2 + (window ? 1 : 0);
+  const int key = ((((n_rows * 16 + rs.cpw) * 16 + rs.nw) * 4096 + rs.nsplit) * 4 + sampler) * 2 + (window ? 1 : 0);
   auto it = x->graphs.find(key);
   if (it == x->graphs.end()) {
     MX_TRY(x, hipStreamSynchronize(st));
     MX_TRY(x, hipStreamBeginCapture(x->cap, hipStreamCaptureModeRelaxed));
-    hipError_t e = enqueue_decode(x, n_rows, nsplit * S, cpw, sampler, window, x->cap, nullptr);
+    hipError_t e = enqueue_decode(x, rs, sampler, window, x->cap, nullptr);
     hipGraph_t g = nullptr;
     hipError_t e2 = hipStreamEndCapture(x->cap, &g);
     MX_TRY(x, e);
@@ -1494,9 +1506,9 @@ extern "C" int mx_llm_decode_profiled(mx_llm* x, int n_rows, void* stream,
   MX_TRY(x, hipSetDevice(x->device));
   if (check_room(x, n_rows)) return MX_ERR_STATE;
   Prof prof;
-  const int ml = decode_max_len(x, n_rows);
-  hipError_t e = enqueue_decode(x, n_rows, ml, att_cpw_auto(x, n_rows, ml), sampler_of(x, n_rows),
-                                window_of(x, n_rows), st, &prof);
+  hipError_t e = enqueue_decode(x, row_set(x, x->h_dec, x->row_slot, x->row_pos, n_rows,
+                                          decode_max_len(x, n_rows), true),
+                                sampler_of(x, n_rows), window_of(x, n_rows), st, &prof);
   mirror_step(x, n_rows);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   for (auto& p : prof.ev) {
@@ -1571,50 +1583,35 @@ extern "C" int mx_llm_bench_attention(mx_llm* x, int L, int n_rows, int cpw, int
 // 0 qkv, 1 o-proj, 2 gate/up, 3 down, 4 the one-row merging o-proj, 5 lm_head.
 static GemvArgs bench_args(mx_llm* x, int which, int li, int n_rows, int merge_pos) {
   const auto& c = x->c;
-  const int H = c.hidden, QD = c.heads * 128;
-  const LayerW& l = x->L[li];
-  GemvArgs g{};
-  attach_ws(x, g);
-  g.R = n_rows; g.eps = c.eps; g.wpb = x->gemv_wpb; g.force_legacy = x->legacy_gemv;
-  g.wdtype = c.wdtype;
+  GemvArgs g;
   if (which == 0) {
-    g.W = l.wqkv; g.Wf = x->rows_frag ? l.wqkv_f : nullptr; g.wscale = l.sqkv;
-    g.N = QD + 2 * c.kv_heads * 128; g.K = H; g.X = x->h_dec; g.norm_w = l.attn_norm;
-    g.rope_cos = x->rope_cos; g.rope_sin = x->rope_sin; g.row_slot = x->row_slot;
-    g.row_pos = x->row_pos; g.kcache = x->kcache + x->kv_layer_elems * li;
-    g.vcache = x->vcache + x->kv_layer_elems * li; g.heads = c.heads; g.kv_heads = c.kv_heads;
-    g.max_pos = c.max_pos; g.Q = x->q;
+    g = qkv_args(x, li, n_rows);
+    g.X = x->h_dec; g.row_slot = x->row_slot; g.row_pos = x->row_pos;
   } else if (which == 1) {
-    g.W = l.wo; g.Wf = x->rows_frag ? l.wo_f : nullptr; g.wscale = l.so; g.N = H; g.K = QD;
-    g.X = x->att; g.Y = x->act; g.rpw = x->rpw_o;
+    g = o_args(x, li, n_rows);
+    g.X = x->att; g.Y = x->act;
   } else if (which == 2) {
-    g.W = l.wgu; g.Wf = x->rows_frag ? l.wgu_f : nullptr; g.wscale = l.sgu; g.N = 2 * c.ffn;
-    g.K = H; g.X = x->h_dec; g.norm_w = l.mlp_norm; g.Y = x->act; g.rpw = x->rpw_gu;
+    g = gu_args(x, li, n_rows);
+    g.X = x->h_dec; g.Y = x->act;
   } else if (which == 3) {
-    g.W = l.wd; g.Wf = x->rows_frag ? l.wd_f : nullptr; g.wscale = l.sd; g.N = H; g.K = c.ffn;
-    g.X = x->act; g.Y = x->q; g.rpw = x->rpw_down;
-  } else if (which == 4) {
-    g.W = l.wo; g.wscale = l.so; g.N = H; g.K = QD; g.X = x->att; g.Y = x->act;
-    g.rpw = x->rpw_o > 0 ? x->rpw_o : 2;
+    g = down_args(x, li, n_rows);
+    g.X = x->act; g.Y = x->q;
+  } else if (which == 4) {  // (row-major weights only, as the one-row kernel reads them)
+    g = o_args(x, li, n_rows);
+    g.Wf = nullptr; g.X = x->att; g.Y = x->act;
+    if (g.rpw == 0) g.rpw = 2;
     g.att_ml = x->part_ml; g.att_acc = x->part_acc; g.att_S = 128;
     g.att_stride = c.max_pos / ATT_S_MIN; g.att_nsm = (merge_pos + 128) / 128;
     g.heads = c.heads; g.kv_heads = c.kv_heads; g.row_pos = x->row_pos;
   } else {  // 5: lm_head + penalty + argmax (the same matrix every launch: 964 MB > MALL)
-    g.W = x->lm; g.Wf = x->rows_frag ? x->lm_f : nullptr; g.wscale = x->slm;
-    g.N = c.vocab; g.K = H; g.X = x->h_dec; g.norm_w = x->norm; g.row_slot = x->row_slot;
-    g.seen = x->seen; g.penalty = x->penalty; g.samp_temp = x->samp_temp; g.best = x->best;
-    g.logits = x->logits; g.logits_all = x->logits_all;
+    g = head_args(x, n_rows);
+    g.X = x->h_dec; g.row_slot = x->row_slot; g.best = x->best; g.logits = x->logits;
   }
-  g.xstride = g.K; g.ystride = g.N;
-  // the step's batch-tile choice (option rows_nt1) for this kind: 0-3 as listed, 4 is the
-  // one-row o-proj (kind bit 1), 5 the lm_head (kind bit 4)
-  nt_cap(x, g, which == 5 ? 4 : which == 4 ? 1 : which, n_rows);
+  // the probes' own: on every kind, also where the step leaves them zero (eps of the residual
+  // projections, ystride of qkv / gate/up / lm_head, wpb and force_legacy of the lm_head)
+  g.eps = c.eps; g.wpb = x->gemv_wpb; g.force_legacy = x->legacy_gemv; g.ystride = g.N;
   // the multi-row qkv as the decode step launches it: raw K-range partials, no seam
-  if (which == 0 && n_rows >= 2 && x->rows_qkv_parts && !x->legacy_gemv &&
-      v4::rows_qkv_nkc_v4(g) <= mx_llm::qkv_nkc_cap) {
-    g.qkv_parts = x->qkv_parts;
-    g.qkv_ss = x->qkv_ss;
-  }
+  if (which == 0) attach_qkv_parts(x, g);
   return g;
 }
 
@@ -1803,6 +1800,66 @@ extern "C" int mx_llm_bench_gemv_trace(mx_llm* x, int which, int n_rows, uint64_
   return MX_OK;
 }
 
+// The options that are one int member with a small set or a range of values (the others, with
+// side effects or cross-checks, are explicit code in mx_llm_set_option).
+struct IntOption {
+  const char* key;
+  int& (*ref)(mx_llm&);
+  int lo, hi;     // allowed: lo..hi ...
+  unsigned only;  // ... and, when non-zero, only the values whose bit is set
+
+  bool allows(int v) const { return v >= lo && v <= hi && (!only || (only >> v) & 1u); }
+  std::string allowed() const {  // "0 or 1", "0, 2 or 4", "0..4096"
+    if (!only && hi - lo > 2) return std::to_string(lo) + ".." + std::to_string(hi);
+    std::string t;
+    for (int v = lo, left = 0; v <= hi; ++v)
+      if (allows(v)) t += (left++ ? ", " : "") + std::to_string(v);
+    const size_t last = t.rfind(", ");
+    return last == std::string::npos ? t : t.replace(last, 2, " or ");
+  }
+};
+#define OPT(m) [](mx_llm& x) -> int& { return x.m; }
+#define BITS2(a, b) (1u << (a) | 1u << (b))
+static const IntOption kIntOptions[] = {
+    {"legacy_gemv", OPT(legacy_gemv), INT_MIN, INT_MAX, 0},  // (any value: zero or not)
+    {"rows_head_mt", OPT(rows_head_mt), 1, 2, 0},
+    {"bench_one_layer", OPT(bench_one_layer), 0, 1, 0},
+    {"engine_dbg", OPT(engine_dbg), 0, 3, 0},
+    {"rows_qkv_parts", OPT(rows_qkv_parts), 0, 1, 0},
+    {"rows_atomic", OPT(rows_atomic), 0, 1, 0},
+    {"grammar_head", OPT(grammar_head), 0, 1, 0},
+    {"head_b1", OPT(head_b1), 0, 1, 0},
+    {"rows_frag", OPT(rows_frag), 0, 1, 0},
+    {"rows_lds_pad", OPT(rows_lds_pad), 0, 128, 0},  // KB
+    {"gemv_wpb", OPT(gemv_wpb), 4, 8, BITS2(4, 8)},
+    {"rpw_o", OPT(rpw_o), 0, 2, 0},
+    {"rpw_down", OPT(rpw_down), 0, 2, 0},
+    {"rpw_gu", OPT(rpw_gu), 0, 4, BITS2(0, 2) | 1u << 4},
+    {"o_merge", OPT(o_merge), 0, 1, 0},
+    {"rows_merge", OPT(rows_merge), 0, 1, 0},
+    {"gemv_balance", OPT(gemv_balance), 0, 1, 0},
+    {"att_b1_nw6", OPT(att_b1_nw6), 0, 1, 0},
+    {"att_nw6", OPT(att_nw6), 0, 1, 0},
+    {"rows_pw", OPT(rows_pw), 1, 2, 0},
+    {"rows_pw_f8", OPT(rows_pw_f8), 1, 2, 0},
+    {"rows_nt1", OPT(rows_nt1), 0, 31, 0},  // a 5-bit kind mask
+    {"rows_nt_max", OPT(rows_nt_max), 0, 4, BITS2(0, 1) | BITS2(2, 4)},
+    {"rows_head_target", OPT(rows_head_target), 0, 4096, 0},
+    {"rows_target", OPT(rows_target), 0, 4096, 0},
+    {"rows_target_qkv", OPT(rows_target_k[0]), 0, 4096, 0},
+    {"rows_target_o", OPT(rows_target_k[1]), 0, 4096, 0},
+    {"rows_target_gu", OPT(rows_target_k[2]), 0, 4096, 0},
+    {"rows_target_down", OPT(rows_target_k[3]), 0, 4096, 0},
+};
+#undef BITS2
+#undef OPT
+
+static const IntOption* int_option(const std::string& key) {
+  for (const IntOption& o : kIntOptions)
+    if (key == o.key) return &o;
+  return nullptr;
+}
+
 extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
   if (!x || !key) return MX_ERR_ARG;
   const std::string k(key);
@@ -1820,11 +1877,6 @@ extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
       MX_TRY(x, hipDeviceSynchronize());
     }
     return MX_OK;
-  } else if (k == "legacy_gemv") {
-    x->legacy_gemv = value;
-  } else if (k == "rows_head_mt") {
-    if (value != 1 && value != 2) MX_FAIL(x, MX_ERR_ARG, "rows_head_mt must be 1 or 2");
-    x->rows_head_mt = value;
   } else if (k == "engine_loaders") {
     if (value != 1 && value != 2) MX_FAIL(x, MX_ERR_ARG, "engine_loaders must be 1 or 2");
     x->engine_loaders = value;
@@ -1868,16 +1920,10 @@ extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
     x->engine_slots = slots;
     x->engine_depth = depth;
     x->b1_engine = en ? 1 : 0;
-  } else if (k == "bench_one_layer") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "bench_one_layer must be 0 or 1");
-    x->bench_one_layer = value;
   } else if (k == "engine_timeout") {
     // (tests force a give-up with a tiny bound; 0 restores the default)
     if (value < 0) MX_FAIL(x, MX_ERR_ARG, "engine_timeout must be >= 0 (ticks of 100 MHz; 0 = 50 ms)");
     x->engine_timeout_ticks = value ? value : 5000000;
-  } else if (k == "engine_dbg") {
-    if (value < 0 || value > 3) MX_FAIL(x, MX_ERR_ARG, "engine_dbg must be 0..3");
-    x->engine_dbg = value;
   } else if (k == "engine_trace") {
     if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "engine_trace must be 0 or 1");
     if (value && !x->eng_trace) {
@@ -1886,84 +1932,25 @@ extern "C" int mx_llm_set_option(mx_llm* x, const char* key, int value) {
       MX_TRY(x, hipMemset(x->eng_trace, 0, (size_t)1024 * x->c.layers * 12 * 8));
     }
     if (!value) x->eng_trace = nullptr;  // (the buffer stays allocated until destroy)
-  } else if (k == "rows_qkv_parts") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "rows_qkv_parts must be 0 or 1");
-    x->rows_qkv_parts = value;
-  } else if (k == "rows_atomic") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "rows_atomic must be 0 or 1");
-    x->rows_atomic = value;
-  } else if (k == "grammar_head") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "grammar_head must be 0 or 1");
-    x->grammar_head = value;
-  } else if (k == "head_b1") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "head_b1 must be 0 or 1");
-    x->head_b1 = value;
-  } else if (k == "rows_frag") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "rows_frag must be 0 or 1");
-    x->rows_frag = value;
-  } else if (k == "rows_lds_pad") {
-    if (value < 0 || value > 128) MX_FAIL(x, MX_ERR_ARG, "rows_lds_pad must be 0..128 (KB)");
-    x->rows_lds_pad = value;
-  } else if (k == "gemv_wpb") {
-    if (value != 4 && value != 8) MX_FAIL(x, MX_ERR_ARG, "gemv_wpb must be 4 or 8");
-    x->gemv_wpb = value;
-  } else if (k == "rpw_o" || k == "rpw_down") {
-    if (value != 0 && value != 1 && value != 2) MX_FAIL(x, MX_ERR_ARG, "rpw must be 0, 1 or 2");
-    (k == "rpw_o" ? x->rpw_o : x->rpw_down) = value;
-  } else if (k == "rpw_gu") {
-    if (value != 0 && value != 2 && value != 4) MX_FAIL(x, MX_ERR_ARG, "rpw_gu must be 0, 2 or 4");
-    x->rpw_gu = value;
-  } else if (k == "o_merge") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "o_merge must be 0 or 1");
-    x->o_merge = value;
-  } else if (k == "rows_merge") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "rows_merge must be 0 or 1");
-    x->rows_merge = value;
-  } else if (k == "gemv_balance") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "gemv_balance must be 0 or 1");
-    x->gemv_balance = value;
   } else if (k == "att_b1_short") {
     if (value < 0 || value > 2) MX_FAIL(x, MX_ERR_ARG, "att_b1_short must be 0, 1 or 2");
     if (value && (x->c.max_pos % 64 || x->max_rows < 2))
       MX_FAIL(x, MX_ERR_ARG, "att_b1_short needs max_pos % 64 == 0 and max(max_batch, max_prefill) >= 2");
     x->att_b1_short = value;
-  } else if (k == "att_b1_nw6") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "att_b1_nw6 must be 0 or 1");
-    x->att_b1_nw6 = value;
-  } else if (k == "att_nw6") {
-    if (value != 0 && value != 1) MX_FAIL(x, MX_ERR_ARG, "att_nw6 must be 0 or 1");
-    x->att_nw6 = value;
   } else if (k == "att_nw" || k == "att_nw_batch") {
     // (one-row overrides with att_cpw > 0 may also take 3- / 6-wave blocks)
     const bool b1_only = (value == 3 || value == 6) && k == "att_nw";
     if (value != 4 && value != 8 && !b1_only) MX_FAIL(x, MX_ERR_ARG, "att_nw must be 4 or 8 (att_nw also 3 / 6)");
     (k == "att_nw" ? x->att_nw_b1 : x->att_nw_batch) = value;
-  } else if (k == "rows_pw" || k == "rows_pw_f8") {
-    if (value < 1 || value > 2) MX_FAIL(x, MX_ERR_ARG, "rows_pw / rows_pw_f8 must be 1 or 2");
-    (k == "rows_pw" ? x->rows_pw : x->rows_pw_f8) = value;
-  } else if (k == "rows_nt1") {
-    if (value < 0 || value > 31) MX_FAIL(x, MX_ERR_ARG, "rows_nt1 must be a 5-bit kind mask");
-    x->rows_nt1 = value;
-  } else if (k == "rows_nt_max") {
-    if (value != 0 && value != 1 && value != 2 && value != 4) MX_FAIL(x, MX_ERR_ARG, "rows_nt_max must be 0, 1, 2 or 4");
-    x->rows_nt_max = value;
-  } else if (k == "rows_head_target") {
-    if (value < 0 || value > 4096) MX_FAIL(x, MX_ERR_ARG, "rows_head_target must be 0..4096");
-    x->rows_head_target = value;
-  } else if (k == "rows_target_qkv" || k == "rows_target_o" || k == "rows_target_gu" ||
-             k == "rows_target_down") {
-    if (value < 0 || value > 4096) MX_FAIL(x, MX_ERR_ARG, k + " must be 0..4096");
-    const int kind = k == "rows_target_qkv" ? 0 : k == "rows_target_o" ? 1 : k == "rows_target_gu" ? 2 : 3;
-    x->rows_target_k[kind] = value;
-  } else if (k == "rows_target") {
-    if (value < 0 || value > 4096) MX_FAIL(x, MX_ERR_ARG, "rows_target must be 0..4096");
-    x->rows_target = value;
   } else if (k == "att_cpw" || k == "att_cpw_batch") {
     const bool any = value == 1 || value == 2 || value == 4 || (value == 0 && k == "att_cpw");
     const bool wide = value == 3 || value == 6 || value == 8;  // 8-wave blocks only
     if (!(any || (wide && k == "att_cpw_batch") || (value == 0 && k == "att_cpw_batch")))
       MX_FAIL(x, MX_ERR_ARG, "att_cpw must be 0 (auto), 1, 2 or 4 (att_cpw_batch also 3/6/8, 0 = auto)");
     (k == "att_cpw" ? x->att_cpw_b1 : x->att_cpw_batch) = value;
+  } else if (const IntOption* o = int_option(k)) {
+    if (!o->allows(value)) MX_FAIL(x, MX_ERR_ARG, k + " must be " + o->allowed());
+    o->ref(*x) = value;
   } else {
     MX_FAIL(x, MX_ERR_ARG, "unknown option " + k);
   }
@@ -2191,15 +2178,40 @@ extern "C" void mx_llm_destroy(mx_llm* x) {
 static const int kRates[4] = {8, 8, 4, 2};
 static const int kDil[3] = {1, 3, 9};
 
-struct mx_snac {
+// What both SNAC contexts hold: the named weights as fp32 on the device, each allocated by its
+// first set, and the bf16 planes finalize derives from the dense ones.
+struct SnacStore {
   int device = 0;
-  int max_frames = 0, max_batch = 0;
   std::string err;
   std::map<std::string, float*> w;
   std::map<std::string, int64_t> expect;
   std::vector<void*> allocs;
-  float* up_packed[4][8] = {};  // per block, per phase: [Cout][2*Cin]
   std::map<std::string, uint16_t*> wbf;  // conv-GEMM weights as bf16 planes [3][M][K]
+};
+
+// (`what`: how the context names its weights in a refusal)
+static int snac_store_set(SnacStore* s, const char* what, const char* name, const void* data,
+                          int64_t numel, int dtype) {
+  const std::string n(name);
+  auto it = s->expect.find(n);
+  if (it == s->expect.end()) MX_FAIL(s, MX_ERR_ARG, std::string("unknown ") + what + " " + n);
+  if (it->second != numel) MX_FAIL(s, MX_ERR_ARG, n + ": bad numel");
+  MX_TRY(s, hipSetDevice(s->device));
+  auto f = s->w.find(n);
+  if (f == s->w.end()) {
+    void* p = nullptr;
+    MX_TRY(s, hipMalloc(&p, numel * 4 + 256));
+    s->allocs.push_back(p);
+    f = s->w.emplace(n, (float*)p).first;
+  }
+  MX_TRY(s, launch_to_f32(f->second, data, numel, dtype == MX_DTYPE_BF16 ? 1 : 0, nullptr));
+  MX_TRY(s, hipDeviceSynchronize());
+  return MX_OK;
+}
+
+struct mx_snac : SnacStore {
+  int max_frames = 0, max_batch = 0;
+  float* up_packed[4][8] = {};  // per block, per phase: [Cout][2*Cin]
   uint16_t* up_bf[4][8] = {};
   int up_delta[4][8][2] = {};
   float *bufA = nullptr, *bufB = nullptr, *bufC = nullptr, *noise = nullptr;
@@ -2279,25 +2291,7 @@ extern "C" int mx_snac_create(int device, int max_frames, int max_batch, mx_snac
 extern "C" int mx_snac_set_weight(mx_snac* s, const char* name, const void* data, int64_t numel,
                                   int dtype) {
   if (!s || !name || !data) return MX_ERR_ARG;
-  const std::string n(name);
-  auto it = s->expect.find(n);
-  if (it == s->expect.end()) MX_FAIL(s, MX_ERR_ARG, "unknown snac weight " + n);
-  if (it->second != numel) MX_FAIL(s, MX_ERR_ARG, n + ": bad numel");
-  MX_TRY(s, hipSetDevice(s->device));
-  float* d = nullptr;
-  auto f = s->w.find(n);
-  if (f == s->w.end()) {
-    void* p = nullptr;
-    MX_TRY(s, hipMalloc(&p, numel * 4 + 256));
-    s->allocs.push_back(p);
-    d = (float*)p;
-    s->w[n] = d;
-  } else {
-    d = f->second;
-  }
-  MX_TRY(s, launch_to_f32(d, data, numel, dtype == MX_DTYPE_BF16 ? 1 : 0, nullptr));
-  MX_TRY(s, hipDeviceSynchronize());
-  return MX_OK;
+  return snac_store_set(s, "snac weight", name, data, numel, dtype);
 }
 
 extern "C" int mx_snac_finalize(mx_snac* s) {
@@ -2581,14 +2575,8 @@ extern "C" void mx_snac_destroy(mx_snac* s) {
 static const int kEncRates[4] = {2, 4, 8, 8};
 static const int kEncMaxFrames = 4096;  // 2048 * 48 floats per frame: offsets stay below 2^31
 
-struct mx_snac_enc {
-  int device = 0;
+struct mx_snac_enc : SnacStore {  // (the planes here: [3][M][Kp])
   int max_frames = 0;
-  std::string err;
-  std::map<std::string, float*> w;
-  std::map<std::string, int64_t> expect;
-  std::vector<void*> allocs;
-  std::map<std::string, uint16_t*> wbf;  // dense weights as bf16 planes [3][M][Kp]
   float *cn[3] = {}, *cn2[3] = {};       // normalised codebooks and their squared lengths
   float *bufA = nullptr, *bufB = nullptr, *bufS = nullptr;
   bool final = false;
@@ -2648,25 +2636,7 @@ extern "C" int mx_snac_enc_set_weight(mx_snac_enc* s, const char* name, const vo
   if (!s || !name || !data) return MX_ERR_ARG;
   if (dtype != MX_DTYPE_F32 && dtype != MX_DTYPE_BF16) MX_FAIL(s, MX_ERR_ARG, "bad dtype");
   if (s->final) MX_FAIL(s, MX_ERR_STATE, "weights are frozen after mx_snac_enc_finalize");
-  const std::string n(name);
-  auto it = s->expect.find(n);
-  if (it == s->expect.end()) MX_FAIL(s, MX_ERR_ARG, "unknown snac encoder weight " + n);
-  if (it->second != numel) MX_FAIL(s, MX_ERR_ARG, n + ": bad numel");
-  MX_TRY(s, hipSetDevice(s->device));
-  float* d = nullptr;
-  auto f = s->w.find(n);
-  if (f == s->w.end()) {
-    void* p = nullptr;
-    MX_TRY(s, hipMalloc(&p, numel * 4 + 256));
-    s->allocs.push_back(p);
-    d = (float*)p;
-    s->w[n] = d;
-  } else {
-    d = f->second;
-  }
-  MX_TRY(s, launch_to_f32(d, data, numel, dtype == MX_DTYPE_BF16 ? 1 : 0, nullptr));
-  MX_TRY(s, hipDeviceSynchronize());
-  return MX_OK;
+  return snac_store_set(s, "snac encoder weight", name, data, numel, dtype);
 }
 
 // fp32 [M][K] on the host -> three bf16 planes [3][M][Kp] on the device (zero columns past K)

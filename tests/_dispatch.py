@@ -3,7 +3,7 @@
 A restatement of the library's host-side dispatch, so that the parity tests' coverage of
 the kernels the bench runs can be checked on the CPU (tests/test_kernel_coverage.py):
 
-* ``capi.hip``: ``att_b1_shape``, ``att_cpw_auto`` / ``att_cpw_pick``, the o-proj merge
+* ``capi.hip``: ``att_b1_shape``, ``att_shape`` / ``att_cpw_pick``, the o-proj merge
   choice of ``enqueue_layers`` (``b1_merge`` / ``rows_merge``), ``enqueue_head``;
 * ``llm_kernels.hip``: ``launch_gemv`` / ``launch_gemv1`` / ``launch_gemv1_t``,
   ``launch_attention``;

@@ -64,9 +64,14 @@ def test_engine_fails_loudly_without_gpu():
 def test_header_option_list_matches_set_option():
     """include/morpheus_mx.h documents exactly the keys capi.hip mx_llm_set_option accepts."""
     src = open(os.path.join(ROOT, "project_morpheus_amd", "csrc", "capi.hip")).read()
+    # the keys with code of their own, and the rows of the table of plain int options
     body = src[src.index('extern "C" int mx_llm_set_option'):]
     body = body[:body.index("unknown option")]
+    assert "int_option(k)" in body
+    table = src[src.index("kIntOptions[] = {"):]
+    table = table[:table.index("\n};")]
     accepted = set(re.findall(r'k == "([a-z0-9_]+)"', body))
+    accepted |= set(re.findall(r'^\s*\{"([a-z0-9_]+)",', table, flags=re.M))
     hdr = open(os.path.join(ROOT, "include", "morpheus_mx.h")).read()
     doc = hdr[hdr.index("Tuning knobs"):hdr.index("int mx_llm_set_option")]
     documented = set(re.findall(r'"([a-z0-9_]+)"', doc))

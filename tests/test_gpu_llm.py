@@ -198,7 +198,7 @@ def test_batched_decode_orpheus_width_32_rows_long_context():
 def test_batched_decode_orpheus_width_32_rows_attention_chunks(prefix_len):
     """configs[2] / [3]'s 32-row decode attention at the contexts where its one split per
     (row, kv head) takes 2 / 3 / 4 chunks of 32 positions per wave (attn_kernel<3,2|3|4,8>,
-    capi.hip att_cpw_auto): a shared prefix of 280 / 560 / 850 ids + ragged tails of 5..36,
+    capi.hip att_shape): a shared prefix of 280 / 560 / 850 ids + ragged tails of 5..36,
     6 steps."""
     cfg = C.OrpheusConfig(layers=2, vocab=16384)
     w = synthetic_llm_weights(cfg, seed=60 + prefix_len)
@@ -460,7 +460,7 @@ def test_batched_decode_vocab_not_multiple_of_4_small(vocab):
 @pytest.mark.parametrize("cpw", [0, 3, 6, 8])
 def test_batched_attention_chunk_counts_long_ragged(cpw):
     """Multi-row attention with several 32-position chunks per wave: ragged contexts of
-    250..481 positions, 8 rows.  cpw 0 = the one-round auto choice (capi.hip att_cpw_auto);
+    250..481 positions, 8 rows.  cpw 0 = the one-round auto choice (capi.hip att_shape);
     3 / 6 / 8 force the 8-wave instantiations (one split up to 768 / 1536 / 2048 positions;
     6 and 8 run the unroll-by-4 runtime chunk loop)."""
     cfg = _cfgs("small")
