@@ -196,6 +196,26 @@ int mx_llm_prefill_chunk(mx_llm* ctx, const mx_prefill_chunk* chunk, void* strea
  * nothing changed) on a slot out of range, dst == src, n_pos < 1 or above the source's length,
  * or a dst bound to an active row. */
 int mx_llm_fork_slot(mx_llm* ctx, int dst_slot, int src_slot, int n_pos, void* stream);
+/* Packed continuation (DESIGN.md §3 "Packed continuation"): a pack of FINAL chunks.  Entry j puts
+ * n_ids ids onto `slot` behind the pos0 positions it holds (pos0 = 0 starts the slot over) and
+ * binds `row`; the layers run once over the sum of the entries' rows.  Afterwards the context
+ * is in the state n_chunks calls of mx_llm_prefill_chunk(last = 1) in entry order would leave,
+ * up to fp32 summation order: K / V, the penalty state over the whole prompt [0, pos0 + n_ids),
+ * slot parameters, grammar origin and sampler counter pos0 + n_ids, the row, the host mirrors.
+ * Every check runs before anything is enqueued.  MX_ERR_ARG on what mx_llm_prefill_batch
+ * refuses (n_chunks outside [1, max_batch], more than max_prefill rows in all, a slot or row
+ * out of range or named twice, an id out of vocab, bad sampling values), on last = 0 (packing
+ * non-final chunks is not offered), pos0 < 0, pos0 + n_ids >= max_pos, or a context (rows in
+ * all, longest pos0 + n_ids) one attention launch cannot merge; MX_ERR_STATE on pos0 > 0 that is
+ * not the slot's mx_llm_slot_len or whose slot is bound to an active row, and before finalize. */
+int mx_llm_prefill_pack(mx_llm* ctx, const mx_prefill_chunk* chunks, int n_chunks, void* stream);
+/* n forks in one device launch: dst[i] holds src[i]'s first n_pos[i] positions afterwards,
+ * exactly as n calls of mx_llm_fork_slot leave them (sources may repeat).  MX_ERR_ARG on n < 1,
+ * n > max_slots or a null pointer; MX_ERR_STATE (nothing enqueued, nothing changed) on what
+ * mx_llm_fork_slot refuses for any triple, a dst named twice, or a dst that is also a src of
+ * the call. */
+int mx_llm_fork_slots(mx_llm* ctx, const int32_t* dst, const int32_t* src, const int32_t* n_pos,
+                      int n, void* stream);
 /* The host mirror: prompt positions `slot` holds (its last prefill's length, the chunks so far,
  * or a fork's n_pos; tokens decoded behind the prompt are not counted). */
 int mx_llm_slot_len(const mx_llm* ctx, int slot, int* n_pos);

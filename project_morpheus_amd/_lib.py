@@ -90,6 +90,9 @@ _SIGS = {
     "mx_llm_prefill_batch": (C.c_int, [_P, C.POINTER(PrefillSeg), C.c_int, _P]),
     "mx_llm_prefill_chunk": (C.c_int, [_P, C.POINTER(PrefillChunk), _P]),
     "mx_llm_fork_slot": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "mx_llm_prefill_pack": (C.c_int, [_P, C.POINTER(PrefillChunk), C.c_int, _P]),
+    "mx_llm_fork_slots": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.c_int, _P]),
     "mx_llm_slot_len": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "mx_llm_decode": (C.c_int, [_P, C.c_int, _P]),
     "mx_llm_check": (C.c_int, [_P, _P]),

@@ -192,6 +192,14 @@ def plan_compaction(rows: List[_Row]) -> List[Tuple[int, int]]:
         hi.idx, lo.idx = i, j
 
 
+# Packed continuation: a pack takes its prefixed members (one ``fork_slots``, their suffixes in
+# the pack's ``prefill_batch``) only from this many of them; fewer take the chunked path
+# (``fork_slot`` + ``prefill_chunk`` each).  Set from profiles/packed_continuation_time.log:
+# the smallest k at which the packed arm's total beats the chunked arm's by more than the
+# chunked arm's own spread (DESIGN.md §7 "Packed continuation").
+PREFIX_PACK_MIN = 2
+
+
 def plan_prefill_packs(lengths: Sequence[int], max_prefill: int, max_k: int) -> List[List[int]]:
     """Packs of a burst of prompts for ``LlmEngine.prefill_batch``: indices into ``lengths`` in
     arrival order, never reordered.  A pack is filled greedily and closed by the first prompt
@@ -401,6 +409,7 @@ class BatchSynthesizer:
         self.packed_prefill = packed_prefill_default() if packed_prefill is None \
             else bool(packed_prefill)
         self.prefill_packs = collections.Counter()  # prefill_batch calls per stream count
+        self.prefix_packs = collections.Counter()   # ... of them, with a member behind a prefix
         self.depth = max(1, BATCH_DEPTH if depth is None else depth)
         # SNAC window coalescing: due windows are held until `snac_min_batch` of them are
         # ready or the oldest has waited `snac_max_hold` decode steps (a stream's first window
@@ -626,34 +635,68 @@ class BatchSynthesizer:
             return True
 
         def admit_packs(cands: List) -> None:
-            """cands: [(row, request, slot, prompt length)] in admission order, slots already
-            taken out of ``free_slots``: one ``prefill_batch`` per pack of the plan."""
-            plan = plan_prefill_packs([n0 for _, _, _, n0 in cands], llm.max_prefill, B)
+            """cands: [(row, request, slot, prompt length, prefix or None)] in admission order,
+            slots already taken out of ``free_slots``, prefixes pinned: per pack of the plan one
+            ``fork_slots`` for its prefixed members, then one ``prefill_batch`` (their suffixes
+            at ``pos0`` = the prefix's length)."""
+            plan = plan_prefill_packs([len(req.prompt_ids) for _, req, _, _, _ in cands],
+                                      llm.max_prefill, B)
+
+            def single(r, req, slot, n0, pre) -> None:
+                if pre is None:
+                    if not prefill_one(r, req, slot, n0):
+                        free_slots.add(slot)
+                    return
+                start_prompt(r, req, slot, pre, n0)
+                if r.req is not req:  # refused on the way
+                    free_slots.add(slot)
+
             for pack in plan:
                 items = [cands[i] for i in pack]
-                segs = [PrefillSegment(
-                    slot=slot, row=r.idx, ids=req.prompt_ids, penalty=req.penalty,
-                    temperature=req.temperature, top_p=req.top_p, seed=req.seed,
-                    top_k=req.top_k, min_p=req.min_p, penalty_last_n=req.penalty_last_n,
-                    grammar=bool(req.grammar)) for r, req, slot, _ in items]
+                forks = [(slot, pre.slot, pre.n) for _, _, slot, _, pre in items if pre is not None]
                 try:
-                    llm.prefill_batch(segs, self.stream)
-                except _lib.MxError as e:
-                    if e.rc != _lib.MX_ERR_ARG:
-                        raise
-                    # refused as a whole (nothing was enqueued): request by request, so the
-                    # bad one fails alone
-                    for r, req, slot, n0 in items:
-                        if not prefill_one(r, req, slot, n0):
-                            free_slots.add(slot)
-                    continue
+                    if 0 < len(forks) < PREFIX_PACK_MIN:
+                        # too few for the pack to pay: they take the chunked path as ever
+                        for it in items:
+                            if it[4] is not None:
+                                single(*it)
+                        items = [it for it in items if it[4] is None]
+                        forks = []
+                        if not items:
+                            continue
+                    segs = [PrefillSegment(
+                        slot=slot, row=r.idx, ids=req.prompt_ids, penalty=req.penalty,
+                        temperature=req.temperature, top_p=req.top_p, seed=req.seed,
+                        top_k=req.top_k, min_p=req.min_p, penalty_last_n=req.penalty_last_n,
+                        grammar=bool(req.grammar), pos0=pre.n if pre is not None else 0)
+                        for r, req, slot, _, pre in items]
+                    try:
+                        if forks:
+                            llm.fork_slots(forks, self.stream)
+                        llm.prefill_batch(segs, self.stream)
+                    except _lib.MxError as e:
+                        if e.rc not in (_lib.MX_ERR_ARG, _lib.MX_ERR_STATE):
+                            raise
+                        # refused as a whole (no prefill was enqueued): request by request, so
+                        # the bad one fails alone
+                        for it in items:
+                            single(*it)
+                        continue
+                finally:
+                    for i in pack:
+                        if cands[i][4] is not None:
+                            cands[i][4].pins -= 1
                 self.prefill_packs[len(items)] += 1
-                for r, req, slot, n0 in items:
+                if forks:
+                    self.prefix_packs[len(items)] += 1
+                for r, req, slot, n0, pre in items:
+                    if pre is not None:
+                        self.prefix_forks[pre.name] += 1
                     bind(r, req, slot, n0)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
-                inflight.append((ev, [(r, req, 0) for r, req, _, _ in items]))
-                for r, _, _, _ in items:
+                inflight.append((ev, [(r, req, 0) for r, req, _, _, _ in items]))
+                for r, _, _, _, _ in items:
                     if r.issued >= r.limit:
                         park(r)
 
@@ -830,7 +873,10 @@ class BatchSynthesizer:
                                            f"{llm.max_pos})")
                     complete(req)
                     continue
-                chunked = pre is not None or n0 > llm.max_prefill
+                # packed prefill takes the prompts that fit one chunk and, behind a ready prefix,
+                # the suffixes that do; everything longer goes chunk by chunk
+                chunked = n0 > llm.max_prefill if pre is None else \
+                    not (self.packed_prefill and len(req.prompt_ids) <= llm.max_prefill)
                 if req.grammar and llm.grammar is None:
                     # the context takes its grammar while idle: the first constrained request
                     # waits for the live streams (and, first in line, holds later arrivals)
@@ -851,7 +897,7 @@ class BatchSynthesizer:
                     req.noise_seed = (self.seed * 1000003 + self._admitted) & _MASK48
                 self._admitted += 1
                 slot = min(free_slots)
-                if chunked:  # (packed prefill takes only prompts that fit one chunk, no prefix)
+                if chunked:
                     start_prompt(r, req, slot, pre, n0)
                     continue
                 if not self.packed_prefill:
@@ -869,7 +915,9 @@ class BatchSynthesizer:
                     complete(req)
                     continue
                 free_slots.discard(slot)
-                cands.append((r, req, slot, n0))
+                if pre is not None:
+                    pre.pins += 1  # (not evicted before its fork is enqueued: admit_packs)
+                cands.append((r, req, slot, n0, pre))
             if cands:
                 admit_packs(cands)
 

@@ -146,6 +146,12 @@ struct mx_llm {
   float* pk_h = nullptr;                  // [max_batch][hidden] the segments' last rows
   float* pk_logits = nullptr;             // [max_batch][vocab] their penalised logits
   std::vector<int32_t> pk_host;           // host copy of the table (one upload per call)
+  // packed continuation (mx_llm_prefill_pack): the id histories [0, pos0) of a call's entries,
+  // back to back (allocated by the first pack behind a history, behind every other buffer)
+  int32_t* pk_hist = nullptr;             // device [max_batch][max_pos]
+  std::vector<int32_t> pk_hist_host;      // its staging copy (one upload per call)
+  int32_t* fork_tab = nullptr;            // device [max_slots] KvFork: mx_llm_fork_slots' table
+                                          // (allocated by its first call, as above)
   // prompt continuation (mx_llm_prefill_chunk / mx_llm_fork_slot): the id history of every slot's
   // prompt lives in plain host memory, written at call time by every prefill entry point and
   // copied by a fork; a final chunk uploads it once (DESIGN.md §3 "Prompt continuation")
@@ -1245,36 +1251,69 @@ extern "C" int mx_llm_prefill_ex(mx_llm* x, int slot, int row, const int32_t* id
 // sampler node, one commit through the rows' remap.  Around them, one launch each: the slots'
 // clear, the per-row / per-segment setup, the window fill (only with a windowed segment), the
 // tail gather + bind, and (kept logits only) their copy to the decode rows' lines.
-extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n_segs,
-                                    void* stream) {
-  if (!x || !segs) return MX_ERR_ARG;
-  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+// Both entry points run this body.  An entry is a final chunk: n ids behind the pos0 positions
+// its slot holds (mx_llm_prefill_batch: every pos0 is 0, and the launches are the ones it has
+// always enqueued).  Behind a history the rows carry pos0 + i, the tail, head and commit sit at
+// pos0 + n, and the penalty state covers [0, pos0 + n): the ids [0, pos0) come from the host id
+// history, staged back to back in pk_hist by one upload (never the host-mapped hist: DESIGN.md
+// §3 "Where the id history lives"), marked by one more launch (whole-sequence segments) or walked
+// by the window fill.
+struct PackEntry {
+  int slot, row, n, pos0;
+  const int32_t* ids;
+  const mx_sampling* sp;
+  const mx_sampling_ext* xe;
+};
+
+static int prefill_pack(mx_llm* x, const std::vector<PackEntry>& es, bool continuation,
+                        void* stream) {
   const auto& c = x->c;
-  if (n_segs < 1 || n_segs > c.max_batch) MX_FAIL(x, MX_ERR_ARG, "bad n_segs");
+  const int n_segs = (int)es.size();
   // every refusal first: a refused call enqueues nothing and changes no host state
   std::vector<char> slot_used(c.max_slots, 0), row_used(c.max_batch, 0);
   long long R64 = 0;
-  int max_n = 0, sampler = SMP_NONE;
-  bool any_window = false, all_constrained = x->gram_on;
-  for (int s = 0; s < n_segs; ++s) {
-    const mx_prefill_seg& g = segs[s];
-    if (!g.ids_host) MX_FAIL(x, MX_ERR_ARG, "segment without ids");
-    if (const char* m = check_sampling(g.params, g.ext)) MX_FAIL(x, MX_ERR_ARG, m);
+  int max_len = 0, max_pos0 = 0, sampler = SMP_NONE;
+  size_t hist_ids = 0;
+  bool any_window = false, any_marks = false, all_constrained = x->gram_on;
+  for (const PackEntry& g : es) {
+    if (!g.ids) MX_FAIL(x, MX_ERR_ARG, "segment without ids");
+    if (const char* m = check_sampling(*g.sp, *g.xe)) MX_FAIL(x, MX_ERR_ARG, m);
     if (g.slot < 0 || g.slot >= c.max_slots || g.row < 0 || g.row >= c.max_batch)
       MX_FAIL(x, MX_ERR_ARG, "slot/row out of range");
     if (slot_used[g.slot] || row_used[g.row])
       MX_FAIL(x, MX_ERR_ARG, "slot/row named twice in one call");
     slot_used[g.slot] = row_used[g.row] = 1;
-    if (g.n_ids < 1 || g.n_ids >= c.max_pos) MX_FAIL(x, MX_ERR_ARG, "bad prompt length");
-    R64 += g.n_ids;
+    if (g.n < 1 || g.n >= c.max_pos) MX_FAIL(x, MX_ERR_ARG, "bad prompt length");
+    R64 += g.n;
     if (R64 > c.max_prefill) MX_FAIL(x, MX_ERR_ARG, "prompts exceed max_prefill rows");
-    if (!ids_in_vocab(x, g.ids_host, g.n_ids)) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
-    max_n = std::max(max_n, g.n_ids);
-    sampler = std::max(sampler, sampler_kind(g.params, g.ext));
-    any_window = any_window || g.ext.penalty_last_n > 0;
+    if (g.pos0 < 0 || (long long)g.pos0 + g.n >= c.max_pos)
+      MX_FAIL(x, MX_ERR_ARG, "chunk does not fit max_pos");
+    if (!ids_in_vocab(x, g.ids, g.n)) MX_FAIL(x, MX_ERR_ARG, "prompt id out of vocab");
+    max_len = std::max(max_len, g.pos0 + g.n);
+    max_pos0 = std::max(max_pos0, g.pos0);
+    hist_ids += (size_t)g.pos0;
+    sampler = std::max(sampler, sampler_kind(*g.sp, *g.xe));
+    any_window = any_window || g.xe->penalty_last_n > 0;
+    any_marks = any_marks || (g.pos0 > 0 && g.xe->penalty_last_n == 0);
     all_constrained = all_constrained && x->slot_grammar[g.slot];
   }
   const int R = (int)R64;
+  if (continuation) {
+    // (pos0 = 0 starts the slot over, as every prefill does)
+    for (const PackEntry& g : es) {
+      if (g.pos0 == 0) continue;
+      if (g.pos0 != x->slot_len[g.slot])
+        MX_FAIL(x, MX_ERR_STATE, "chunk at position " + std::to_string(g.pos0) +
+                                     ": the slot holds " + std::to_string(x->slot_len[g.slot]));
+      if (row_of_slot(x, g.slot) >= 0)
+        MX_FAIL(x, MX_ERR_STATE, "chunk onto a slot bound to an active row");
+    }
+    // the launch's own argument checks, as mx_llm_prefill_chunk makes them
+    const AttShape sh = att_shape(x, R, max_len);
+    const int stride = sh.S() < ATT_S_MIN ? c.max_pos / 64 : c.max_pos / ATT_S_MIN;
+    if (sh.nsplit > ATT_MAX_SPLITS || (c.max_pos + sh.S() - 1) / sh.S() > stride)
+      MX_FAIL(x, MX_ERR_ARG, "pack: the context needs more attention splits than one launch merges");
+  }
   hipStream_t st = (hipStream_t)stream;
   MX_TRY(x, hipSetDevice(x->device));
   const size_t seg_words = (size_t)c.max_batch * (sizeof(PackSeg) / 4);
@@ -1285,22 +1324,30 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
     MX_TRY(x, x->alloc(&x->pk_h, (size_t)c.max_batch * c.hidden));
     MX_TRY(x, x->alloc(&x->pk_logits, (size_t)c.max_batch * c.vocab));
   }
-  // the table: the segments, then their rows
+  if (hist_ids && !x->pk_hist) MX_TRY(x, x->alloc(&x->pk_hist, (size_t)c.max_batch * c.max_pos));
+  // the table: the segments, then their rows; the histories back to back
   x->pk_host.assign(seg_words + (size_t)R * (sizeof(PackRow) / 4), 0);
+  x->pk_hist_host.resize(hist_ids);
   PackSeg* hs = reinterpret_cast<PackSeg*>(x->pk_host.data());
   PackRow* hr = reinterpret_cast<PackRow*>(x->pk_host.data() + seg_words);
+  size_t hoff = 0;
   for (int s = 0, r = 0; s < n_segs; ++s) {
-    const mx_prefill_seg& g = segs[s];
+    const PackEntry& g = es[s];
     PackSeg& t = hs[s];
-    t.slot = g.slot; t.row = g.row; t.first = r; t.n = g.n_ids;
+    t.slot = g.slot; t.row = g.row; t.first = r; t.n = g.n;
     // a constrained slot counts its phases from the prompt's end (-1: unconstrained)
-    t.origin = x->gram_on && x->slot_grammar[g.slot] ? g.n_ids : -1;
-    t.top_k = g.ext.top_k; t.last_n = g.ext.penalty_last_n;
-    t.pen = g.params.repetition_penalty; t.temp = g.params.temperature;
-    t.top_p = g.params.top_p < 1.f ? g.params.top_p : 1.f; t.min_p = g.ext.min_p;
-    t.seed_lo = (uint32_t)g.params.seed; t.seed_hi = (uint32_t)(g.params.seed >> 32);
-    for (int i = 0; i < g.n_ids; ++i, ++r)
-      hr[r] = PackRow{g.ids_host[i], g.slot, i, g.ext.penalty_last_n > 0 ? 0 : 1};
+    t.origin = x->gram_on && x->slot_grammar[g.slot] ? g.pos0 + g.n : -1;
+    t.top_k = g.xe->top_k; t.last_n = g.xe->penalty_last_n;
+    t.pen = g.sp->repetition_penalty; t.temp = g.sp->temperature;
+    t.top_p = g.sp->top_p < 1.f ? g.sp->top_p : 1.f; t.min_p = g.xe->min_p;
+    t.seed_lo = (uint32_t)g.sp->seed; t.seed_hi = (uint32_t)(g.sp->seed >> 32);
+    t.pos0 = g.pos0; t.hist = (int32_t)hoff;
+    if (g.pos0 > 0)
+      std::memcpy(x->pk_hist_host.data() + hoff, x->slot_ids.data() + (size_t)g.slot * c.max_pos,
+                  (size_t)g.pos0 * 4);
+    hoff += (size_t)g.pos0;
+    for (int i = 0; i < g.n; ++i, ++r)
+      hr[r] = PackRow{g.ids[i], g.slot, g.pos0 + i, g.xe->penalty_last_n > 0 ? 0 : 1};
   }
   const PackSeg* dsegs = reinterpret_cast<const PackSeg*>(x->pk_tab);
   const PackRow* drows = reinterpret_cast<const PackRow*>(x->pk_tab + seg_words);
@@ -1308,6 +1355,9 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
   // when the call returns, so the next call may rebuild the table)
   MX_TRY(x, hipMemcpyAsync(x->pk_tab, x->pk_host.data(), x->pk_host.size() * 4,
                            hipMemcpyHostToDevice, st));
+  if (hist_ids)
+    MX_TRY(x, hipMemcpyAsync(x->pk_hist, x->pk_hist_host.data(), hist_ids * 4,
+                             hipMemcpyHostToDevice, st));
   MX_TRY(x, launch_pack_clear(dsegs, n_segs, c.vocab, x->seen, x->recent, st));
   PackSetupArgs ps{};
   ps.rows = drows; ps.segs = dsegs; ps.R = R; ps.n_segs = n_segs; ps.embed = x->embed;
@@ -1317,11 +1367,13 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
   ps.top_k = x->samp_top_k; ps.min_p = x->samp_min_p; ps.last_n = x->last_n;
   ps.origin = x->gram_on ? x->gram_origin : nullptr;
   MX_TRY(x, launch_pack_setup(ps, st));
-  // the attention grid is sized by the longest segment; shorter rows leave its later splits
-  MX_TRY(x, enqueue_layers(x, row_set(x, x->h_pre, x->pre_slot, x->pre_pos, R, max_n, false),
+  // the attention grid is sized by the longest context; shorter rows leave its later splits
+  MX_TRY(x, enqueue_layers(x, row_set(x, x->h_pre, x->pre_slot, x->pre_pos, R, max_len, false),
                            st, nullptr));
+  if (any_marks)
+    MX_TRY(x, launch_pack_hist_marks(dsegs, x->pk_hist, n_segs, max_pos0, c.vocab, x->seen, st));
   if (any_window)
-    MX_TRY(x, launch_pack_window(drows, dsegs, n_segs, c.vocab, x->seen, x->recent, st));
+    MX_TRY(x, launch_pack_window(drows, dsegs, x->pk_hist, n_segs, c.vocab, x->seen, x->recent, st));
   int32_t *hslot = x->pk_idx, *hpos = x->pk_idx + c.max_batch, *hrow = x->pk_idx + 2 * c.max_batch;
   PackTailArgs pt{};
   pt.segs = dsegs; pt.h = x->h_pre; pt.hidden = c.hidden; pt.head_h = x->pk_h;
@@ -1339,11 +1391,39 @@ extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n
   cm.row_token = x->row_token; cm.h = x->h_dec;
   MX_TRY(x, launch_commit(cm, n_segs, st));
   for (int s = 0; s < n_segs; ++s) {
-    const mx_prefill_seg& g = segs[s];
-    bind_row(x, g.row, g.slot, g.n_ids, sampler_kind(g.params, g.ext), hs[s].origin);
-    record_prompt(x, g.slot, 0, g.ids_host, g.n_ids);
+    const PackEntry& g = es[s];
+    bind_row(x, g.row, g.slot, g.pos0 + g.n, sampler_kind(*g.sp, *g.xe), hs[s].origin);
+    record_prompt(x, g.slot, g.pos0, g.ids, g.n);
   }
   return MX_OK;
+}
+
+extern "C" int mx_llm_prefill_batch(mx_llm* x, const mx_prefill_seg* segs, int n_segs,
+                                    void* stream) {
+  if (!x || !segs) return MX_ERR_ARG;
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  if (n_segs < 1 || n_segs > x->c.max_batch) MX_FAIL(x, MX_ERR_ARG, "bad n_segs");
+  std::vector<PackEntry> es(n_segs);
+  for (int s = 0; s < n_segs; ++s) {
+    const mx_prefill_seg& g = segs[s];
+    es[s] = PackEntry{g.slot, g.row, g.n_ids, 0, g.ids_host, &g.params, &g.ext};
+  }
+  return prefill_pack(x, es, false, stream);
+}
+
+// A pack of final chunks (DESIGN.md §3 "Packed continuation").
+extern "C" int mx_llm_prefill_pack(mx_llm* x, const mx_prefill_chunk* chunks, int n_chunks,
+                                   void* stream) {
+  if (!x || !chunks) return MX_ERR_ARG;
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  if (n_chunks < 1 || n_chunks > x->c.max_batch) MX_FAIL(x, MX_ERR_ARG, "bad n_segs");
+  std::vector<PackEntry> es(n_chunks);
+  for (int s = 0; s < n_chunks; ++s) {
+    const mx_prefill_chunk& g = chunks[s];
+    if (!g.last) MX_FAIL(x, MX_ERR_ARG, "pack: every chunk must be its prompt's last");
+    es[s] = PackEntry{g.slot, g.row, g.n_ids, g.pos0, g.ids_host, &g.params, &g.ext};
+  }
+  return prefill_pack(x, es, true, stream);
 }
 
 // Prompt continuation: a chunk of a prompt behind the pos0 positions its slot already holds
@@ -1406,6 +1486,58 @@ extern "C" int mx_llm_fork_slot(mx_llm* x, int dst, int src, int n_pos, void* st
   std::memcpy(x->slot_ids.data() + (size_t)dst * c.max_pos,
               x->slot_ids.data() + (size_t)src * c.max_pos, (size_t)n_pos * 4);
   x->slot_len[dst] = n_pos;
+  return MX_OK;
+}
+
+// n forks as one kv_fork_many_kernel launch: the table goes up once, the id histories are
+// copied on the host.  The refusals are mx_llm_fork_slot's per triple, plus the two that keep
+// the launch's units independent: no dst twice, no dst that the call also reads.
+extern "C" int mx_llm_fork_slots(mx_llm* x, const int32_t* dst, const int32_t* src,
+                                 const int32_t* n_pos, int n, void* stream) {
+  if (!x) return MX_ERR_ARG;
+  const auto& c = x->c;
+  if (!dst || !src || !n_pos || n < 1 || n > c.max_slots)
+    MX_FAIL(x, MX_ERR_ARG, "fork_slots: need 1 <= n <= max_slots and three arrays");
+  if (!x->final) MX_FAIL(x, MX_ERR_STATE, "not finalized");
+  std::vector<char> is_dst(c.max_slots, 0), is_src(c.max_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (dst[i] < 0 || dst[i] >= c.max_slots || src[i] < 0 || src[i] >= c.max_slots)
+      MX_FAIL(x, MX_ERR_STATE, "fork: slot out of range");
+    if (dst[i] == src[i]) MX_FAIL(x, MX_ERR_STATE, "fork: dst is src");
+    if (n_pos[i] < 1 || n_pos[i] > x->slot_len[src[i]])
+      MX_FAIL(x, MX_ERR_STATE, "fork of " + std::to_string(n_pos[i]) +
+                                   " positions: the source holds " +
+                                   std::to_string(x->slot_len[src[i]]));
+    if (row_of_slot(x, dst[i]) >= 0) MX_FAIL(x, MX_ERR_STATE, "fork: dst is bound to an active row");
+    if (is_dst[dst[i]]) MX_FAIL(x, MX_ERR_STATE, "fork: dst named twice in one call");
+    is_dst[dst[i]] = 1;
+    is_src[src[i]] = 1;
+  }
+  for (int i = 0; i < n; ++i)
+    if (is_src[dst[i]]) MX_FAIL(x, MX_ERR_STATE, "fork: dst is a src of the same call");
+  MX_TRY(x, hipSetDevice(x->device));
+  if (!x->fork_tab) MX_TRY(x, x->alloc(&x->fork_tab, (size_t)c.max_slots * (sizeof(KvFork) / 4)));
+  std::vector<KvFork> tab(n);
+  int max_chunks = 0;
+  for (int i = 0; i < n; ++i) {
+    tab[i] = KvFork{dst[i], src[i], (n_pos[i] + 31) / 32, 0};
+    max_chunks = std::max(max_chunks, tab[i].chunks);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // (pageable source: the runtime has read it when the call returns)
+  MX_TRY(x, hipMemcpyAsync(x->fork_tab, tab.data(), (size_t)n * sizeof(KvFork),
+                           hipMemcpyHostToDevice, st));
+  KvForkManyArgs a{};
+  a.kcache = x->kcache; a.vcache = x->vcache; a.kv_layer_elems = x->kv_layer_elems;
+  a.layers = c.layers; a.kv_heads = c.kv_heads; a.max_pos = c.max_pos;
+  a.runs = 2 * c.layers * c.kv_heads;
+  a.forks = reinterpret_cast<const KvFork*>(x->fork_tab); a.n = n; a.max_chunks = max_chunks;
+  MX_TRY(x, launch_kv_fork_many(a, x->cus, st));
+  for (int i = 0; i < n; ++i) {
+    std::memcpy(x->slot_ids.data() + (size_t)dst[i] * c.max_pos,
+                x->slot_ids.data() + (size_t)src[i] * c.max_pos, (size_t)n_pos[i] * 4);
+    x->slot_len[dst[i]] = n_pos[i];
+  }
   return MX_OK;
 }
 

@@ -1385,32 +1385,57 @@ hipError_t launch_pack_setup(const PackSetupArgs& a, hipStream_t st) {
 }
 
 // window_prefill_kernel for every windowed segment of a pack: block s, thread 0 walks the
-// segment's last min(n, N) ids serially (the slot's bytes and ring were zeroed by pack_clear).
+// prompt's last min(pos0 + n, N) positions serially (the slot's bytes and ring were zeroed by
+// pack_clear).  The prompt is the pos0 staged history ids, then the segment's rows, so the
+// window may lie in either or straddle the seam; the ring cell is the absolute position's.
 __global__ __launch_bounds__(64) void pack_window_kernel(const PackRow* rows, const PackSeg* segs,
-                                                         int vocab, uint8_t* seen,
-                                                         int32_t* recent) {
+                                                         const int32_t* hist, int vocab,
+                                                         uint8_t* seen, int32_t* recent) {
   if (threadIdx.x != 0) return;
   const PackSeg s = segs[blockIdx.x];
   if (s.last_n <= 0) return;
   int32_t* ring = recent + (size_t)s.slot * PEN_RING;
   uint8_t* cnt = seen + (size_t)s.slot * vocab;
-  for (int p = max(0, s.n - s.last_n); p < s.n; ++p) {
-    const int tok = rows[s.first + p].id;
+  const int end = s.pos0 + s.n;
+  for (int p = max(0, end - s.last_n); p < end; ++p) {
+    const int tok = p < s.pos0 ? hist[s.hist + p] : rows[s.first + p - s.pos0].id;
     ++cnt[tok];
     ring[p & (PEN_RING - 1)] = tok;
   }
 }
 
-hipError_t launch_pack_window(const PackRow* rows, const PackSeg* segs, int n_segs, int vocab,
-                              uint8_t* seen, int32_t* recent, hipStream_t st) {
-  hipLaunchKernelGGL(pack_window_kernel, dim3(n_segs), dim3(64), 0, st, rows, segs, vocab, seen,
-                     recent);
+hipError_t launch_pack_window(const PackRow* rows, const PackSeg* segs, const int32_t* hist,
+                              int n_segs, int vocab, uint8_t* seen, int32_t* recent,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(pack_window_kernel, dim3(n_segs), dim3(64), 0, st, rows, segs, hist, vocab,
+                     seen, recent);
   return hipGetLastError();
 }
 
-// The tail's inputs: segment s's last prompt row, with its slot and position n - 1, becomes
-// row s of the contiguous head input; its decode row is bound to (slot, n - 1), which the
-// commit advances to n.  Grid n_segs, block 256.
+// Whole-sequence penalty state of the segments behind a history: seen[slot][id] = 1 for the
+// pos0 staged ids of every segment without a window (same-value byte stores from many lanes, as
+// mark_seen_kernel; the rows' own ids are marked by pack_setup_kernel).  Grid (x, segment).
+__global__ __launch_bounds__(256) void pack_hist_marks_kernel(const PackSeg* segs,
+                                                              const int32_t* hist, int vocab,
+                                                              uint8_t* seen) {
+  const PackSeg s = segs[blockIdx.y];
+  if (s.last_n > 0) return;
+  uint8_t* mark = seen + (size_t)s.slot * vocab;
+  const int32_t* ids = hist + s.hist;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < s.pos0; i += gridDim.x * 256) mark[ids[i]] = 1;
+}
+
+hipError_t launch_pack_hist_marks(const PackSeg* segs, const int32_t* hist, int n_segs,
+                                  int max_pos0, int vocab, uint8_t* seen, hipStream_t st) {
+  const int gx = std::max(1, std::min(16, (max_pos0 + 255) / 256));
+  hipLaunchKernelGGL(pack_hist_marks_kernel, dim3(gx, n_segs), dim3(256), 0, st, segs, hist,
+                     vocab, seen);
+  return hipGetLastError();
+}
+
+// The tail's inputs: segment s's last prompt row, with its slot and position pos0 + n - 1,
+// becomes row s of the contiguous head input; its decode row is bound to (slot, pos0 + n - 1),
+// which the commit advances to pos0 + n.  Grid n_segs, block 256.
 __global__ __launch_bounds__(256) void pack_tail_kernel(PackTailArgs a) {
   const int k = blockIdx.x;
   const PackSeg s = a.segs[k];
@@ -1419,11 +1444,11 @@ __global__ __launch_bounds__(256) void pack_tail_kernel(PackTailArgs a) {
   for (int c = threadIdx.x; c < (a.hidden >> 2); c += 256) dst[c] = src[c];
   if (threadIdx.x == 0) {
     a.head_slot[k] = s.slot;
-    a.head_pos[k] = s.n - 1;
+    a.head_pos[k] = s.pos0 + s.n - 1;
     a.head_row[k] = s.row;
     a.head_best[k] = 0ull;
     a.row_slot[s.row] = s.slot;
-    a.row_pos[s.row] = s.n - 1;
+    a.row_pos[s.row] = s.pos0 + s.n - 1;
   }
 }
 
@@ -1525,6 +1550,63 @@ hipError_t launch_kv_fork(const KvForkArgs& a, int cus, hipStream_t st) {
   const long long pairs = ((long long)a.runs * a.chunks + 1) / 2;
   const int grid = (int)std::min<long long>(pairs, (long long)std::max(cus, 1) * 8);
   hipLaunchKernelGGL(kv_fork_kernel, dim3(grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// n forks in one launch.  A unit is (chunk c of the runs, fork i), c = run * chunks_i + chunk over
+// fork i's runs * chunks_i chunks, numbered u = c * n + i: the forks of one chunk are
+// neighbours, so a source that several forks share is read from HBM once and from L2 / the
+// Infinity Cache for the others.  Forks shorter than the longest leave their later units
+// (c >= runs * chunks_i) out.  A block takes unit pairs grid-stride; as in kv_fork_kernel every
+// lane issues its four 16-byte loads before the first store (a unit that is left out loads its
+// fork's chunk 0, which exists, and stores nothing).  The host has checked that no dst is a src
+// or another dst: no unit writes what another reads or writes.
+__global__ __launch_bounds__(256) void kv_fork_many_kernel(KvForkManyArgs a) {
+  const long long total = (long long)a.runs * a.max_chunks * a.n;
+  const int per_kind = a.layers * a.kv_heads;
+  for (long long u = 2ll * blockIdx.x; u < total; u += 2ll * gridDim.x) {
+    const uint4* s[2];
+    uint4* d[2];
+    bool on[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      on[j] = u + j < total;
+      const long long uj = on[j] ? u + j : u;
+      const KvFork f = a.forks[(int)(uj % a.n)];
+      long long c = uj / a.n;
+      if (c >= (long long)a.runs * f.chunks) {
+        on[j] = false;
+        c = 0;
+      }
+      const int run = (int)(c / f.chunks), ch = (int)(c % f.chunks);
+      const int kind = run / per_kind, rem = run % per_kind;
+      const int layer = rem / a.kv_heads, kvh = rem % a.kv_heads;
+      uint16_t* base = (kind ? a.vcache : a.kcache) + a.kv_layer_elems * layer;
+      const size_t chunk_off = (size_t)ch * 4096;
+      s[j] = reinterpret_cast<const uint4*>(
+          base + ((size_t)f.src * a.kv_heads + kvh) * a.max_pos * 128 + chunk_off);
+      d[j] = reinterpret_cast<uint4*>(
+          base + ((size_t)f.dst * a.kv_heads + kvh) * a.max_pos * 128 + chunk_off);
+    }
+    const uint4 v0 = s[0][threadIdx.x], v1 = s[0][threadIdx.x + 256];
+    const uint4 v2 = s[1][threadIdx.x], v3 = s[1][threadIdx.x + 256];
+    if (on[0]) {
+      d[0][threadIdx.x] = v0;
+      d[0][threadIdx.x + 256] = v1;
+    }
+    if (on[1]) {
+      d[1][threadIdx.x] = v2;
+      d[1][threadIdx.x + 256] = v3;
+    }
+  }
+}
+
+hipError_t launch_kv_fork_many(const KvForkManyArgs& a, int cus, hipStream_t st) {
+  if (a.n < 1 || a.max_chunks < 1 || a.max_chunks > a.max_pos / 32 || a.runs < 1 || !a.forks)
+    return hipErrorInvalidValue;
+  const long long pairs = ((long long)a.runs * a.max_chunks * a.n + 1) / 2;
+  const int grid = (int)std::min<long long>(pairs, (long long)std::max(cus, 1) * 8);
+  hipLaunchKernelGGL(kv_fork_many_kernel, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -230,11 +230,13 @@ hipError_t launch_scatter_rows(void* dst, const void* src, const int32_t* dmap, 
 struct PackSeg {
   int32_t slot, row;       // KV slot, decode row the stream is bound to
   int32_t first, n;        // the segment's rows: [first, first + n) of the row set
-  int32_t origin;          // grammar origin of the slot (n, or -1: unconstrained)
+  int32_t origin;          // grammar origin of the slot (pos0 + n, or -1: unconstrained)
   int32_t top_k, last_n;   // extras (0 = neutral)
   float pen, temp, top_p, min_p;
   uint32_t seed_lo, seed_hi;
-  int32_t pad[3];
+  int32_t pos0;            // positions the slot holds in front of the rows (mx_llm_prefill_pack)
+  int32_t hist;            // ... whose ids [0, pos0) start here in the staged histories
+  int32_t pad;
 };
 static_assert(sizeof(PackSeg) == 64, "PackSeg is uploaded as 16 words");
 struct PackRow {
@@ -274,9 +276,16 @@ hipError_t launch_pack_clear(const PackSeg* segs, int n_segs, int vocab, uint8_t
 // per row: pre_slot / pre_pos, the embedding gather and the seen mark; per segment: the slot's
 // generation parameters, extras and grammar origin (one launch, grid R + n_segs)
 hipError_t launch_pack_setup(const PackSetupArgs& a, hipStream_t st);
-// window counts and ring of every windowed segment (last_n > 0; one block each, serial)
-hipError_t launch_pack_window(const PackRow* rows, const PackSeg* segs, int n_segs, int vocab,
-                              uint8_t* seen, int32_t* recent, hipStream_t st);
+// window counts and ring of every windowed segment (last_n > 0; one block each, serial) over
+// positions max(0, pos0 + n - last_n) .. pos0 + n - 1: below pos0 from `hist` (the staged
+// histories; null when no segment has one), from there on from the rows
+hipError_t launch_pack_window(const PackRow* rows, const PackSeg* segs, const int32_t* hist,
+                              int n_segs, int vocab, uint8_t* seen, int32_t* recent,
+                              hipStream_t st);
+// seen[slot][hist[seg.hist + i]] = 1, i < pos0, for every whole-sequence segment (last_n = 0)
+// behind a history (one launch; max_pos0 sizes the grid)
+hipError_t launch_pack_hist_marks(const PackSeg* segs, const int32_t* hist, int n_segs,
+                                  int max_pos0, int vocab, uint8_t* seen, hipStream_t st);
 hipError_t launch_pack_tail(const PackTailArgs& a, int n_segs, hipStream_t st);
 // dst[rows[k]][0, V) = src[k][0, V): the kept logits to the decode rows' own lines
 hipError_t launch_pack_logits(float* dst, const float* src, const int32_t* rows, int n_segs,
@@ -295,6 +304,26 @@ struct KvForkArgs {
 // grid is sized from `cus`).  hipErrorInvalidValue on chunks outside [1, max_pos / 32] or
 // src == dst.
 hipError_t launch_kv_fork(const KvForkArgs& a, int cus, hipStream_t st);
+// n forks in one launch (mx_llm_fork_slots): the fork table is read from device memory
+struct KvFork {
+  int32_t dst, src;        // KV slots
+  int32_t chunks;          // ceil(n_pos / 32)
+  int32_t pad;
+};
+static_assert(sizeof(KvFork) == 16, "KvFork is uploaded as 4 words");
+struct KvForkManyArgs {
+  uint16_t* kcache;
+  uint16_t* vcache;
+  size_t kv_layer_elems;
+  int layers, kv_heads, max_pos;
+  int runs;                // 2 * layers * kv_heads
+  const KvFork* forks;     // device, [n]
+  int n;
+  int max_chunks;          // the largest `chunks` of the table
+};
+// hipErrorInvalidValue on n < 1 or max_chunks outside [1, max_pos / 32]; the caller has checked
+// the table (slots in range, every dst distinct and no src)
+hipError_t launch_kv_fork_many(const KvForkManyArgs& a, int cus, hipStream_t st);
 // seen[slot][ids[i]] = 1, i < n (the whole-sequence penalty state from an id history)
 hipError_t launch_mark_seen(const int32_t* ids, int n, int slot, int vocab, uint8_t* seen,
                             hipStream_t st);

@@ -44,7 +44,9 @@ def _dtype_code(t: torch.Tensor) -> int:
 
 @dataclass
 class PrefillSegment:
-    """One stream of ``LlmEngine.prefill_batch``: ``prefill``'s arguments as fields."""
+    """One stream of ``LlmEngine.prefill_batch``: ``prefill``'s arguments as fields.  ``pos0``:
+    the ids go behind the ``pos0`` positions the slot already holds (a forked prefix), as a final
+    ``prefill_chunk``'s do."""
     slot: int
     row: int
     ids: Sequence[int]
@@ -56,6 +58,7 @@ class PrefillSegment:
     min_p: float = 0.0
     penalty_last_n: int = 0
     grammar: bool = False
+    pos0: int = 0
 
 
 class LlmEngine:
@@ -129,26 +132,32 @@ class LlmEngine:
         """Packed prefill (mx_llm_prefill_batch): admit several streams in one pass over the
         weights.  ``segments``: ``PrefillSegment`` objects or dicts with ``slot``, ``row``,
         ``ids``, ``penalty`` and any of ``prefill``'s keywords.  Leaves the engine as the same
-        ``prefill`` calls in order would; a call the device refuses changes nothing."""
+        ``prefill`` calls in order would; a call the device refuses changes nothing.  Segments
+        with ``pos0 > 0`` continue their slots (mx_llm_prefill_pack: the state the same final
+        ``prefill_chunk`` calls in order would leave)."""
         segs = [s if isinstance(s, PrefillSegment) else PrefillSegment(**s) for s in segments]
         for s in segs:
             if bool(s.grammar) != self._slot_grammar.get(s.slot, False) and \
                     0 <= s.slot < self.max_slots:
                 self._check(self.lib.mx_llm_set_slot_grammar(self.h, s.slot, int(bool(s.grammar))))
                 self._slot_grammar[s.slot] = bool(s.grammar)
-        arr = (_lib.PrefillSeg * max(1, len(segs)))()
+        # behind a history the pack of final chunks; every pos0 = 0: the packed prefill as ever
+        pack = any(int(s.pos0) != 0 for s in segs)
+        arr = ((_lib.PrefillChunk if pack else _lib.PrefillSeg) * max(1, len(segs)))()
         keep = []  # the id arrays live until the call returns
         for a, s in zip(arr, segs):
             ids = np.ascontiguousarray(np.asarray(s.ids, dtype=np.int32))
             keep.append(ids)
             a.slot, a.row, a.ids_host, a.n_ids = int(s.slot), int(s.row), ids.ctypes.data, len(ids)
+            if pack:
+                a.pos0, a.last = int(s.pos0), 1
             a.params = _lib.Sampling(temperature=float(s.temperature), top_p=float(s.top_p),
                                      repetition_penalty=float(s.penalty),
                                      seed=int(s.seed) & (2**64 - 1))
             a.ext = _lib.SamplingExt(top_k=int(s.top_k), min_p=float(s.min_p),
                                      penalty_last_n=int(s.penalty_last_n))
-        self._check(self.lib.mx_llm_prefill_batch(self.h, arr, len(segs),
-                                                  C.c_void_p(stream.cuda_stream)))
+        call = self.lib.mx_llm_prefill_pack if pack else self.lib.mx_llm_prefill_batch
+        self._check(call(self.h, arr, len(segs), C.c_void_p(stream.cuda_stream)))
 
     def prefill_chunk(self, slot: int, ids: Sequence[int], pos0: int, stream, *,
                       last: bool = False, row: Optional[int] = None, penalty: float = 1.1,
@@ -184,6 +193,15 @@ class LlmEngine:
         layer and the id history; one device copy ordered on ``stream``)."""
         self._check(self.lib.mx_llm_fork_slot(self.h, int(dst), int(src), int(n_pos),
                                               C.c_void_p(stream.cuda_stream)))
+
+    def fork_slots(self, pairs: Sequence, stream) -> None:
+        """``fork_slot`` for every ``(dst, src, n_pos)`` of ``pairs`` in one device launch
+        (mx_llm_fork_slots).  Sources may repeat; no ``dst`` may appear twice or as a ``src``.  A
+        call the device refuses changes nothing."""
+        tab = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.int32).reshape(-1, 3).T)
+        ptr = [tab[i].ctypes.data_as(C.POINTER(C.c_int32)) for i in range(3)]
+        self._check(self.lib.mx_llm_fork_slots(self.h, ptr[0], ptr[1], ptr[2], tab.shape[1],
+                                               C.c_void_p(stream.cuda_stream)))
 
     def slot_len(self, slot: int) -> int:
         """Prompt positions ``slot`` holds (the library's host mirror)."""
