@@ -29,12 +29,14 @@ engine, one request per thread (Orpheus-TTS/orpheus_tts_pypi/orpheus_tts/engine_
 
 Two drivers share the loop: ``run(requests)`` (offline: arrival times, bench / long-form
 jobs) and ``start()`` + ``submit(request) -> StreamHandle`` (online: the per-GPU service the
-adapters use; a background thread owns the GPU).
+adapters use; a background thread owns the GPU).  One run of it is a ``_Loop``: the run's state
+and, as methods, the steps ``iterate`` calls in order: poll, cancellations, control,
+advance_prefixes, admit, advance_prompts, compact, issue, collect, windows, drain, announce.  A
+request passes admission as an ``_Admission`` and reaches the engine as ``request_segment`` of it.
 """
 from __future__ import annotations
 
 import collections
-
 import queue
 import threading
 import time
@@ -50,14 +52,7 @@ from .config import (BATCH_DEPTH, ORPHEUS_GRAMMAR, SNAC_MAX_HOLD, SNAC_MIN_BATCH
                      packed_prefill_default)
 from .engine import (SAMPLES_PER_FRAME, SLICE_HI, SLICE_LO, LlmEngine, PrefillSegment,
                      SnacDecoder)
-from .schedule import WindowScheduler, code_of_id, frames_for_slice
-
-_MASK48 = 0xFFFFFFFFFFFF
-
-
-def window_seed(noise_seed: int, j: int) -> int:
-    """Noise seed of a stream's j-th SNAC window (batching-invariant)."""
-    return (noise_seed * 1000003 + j) & _MASK48
+from .schedule import WindowScheduler, code_of_id, frames_for_slice, window_seed
 
 
 @dataclass(eq=False)
@@ -150,6 +145,26 @@ def check_prefix(prefix) -> None:
         raise ValueError(f"prefix must be a non-empty string, got {prefix!r}")
 
 
+def request_segment(req: StreamRequest, slot: int, row: int, pos0: int = 0) -> PrefillSegment:
+    """``req``'s prompt and generation parameters as the engine takes them (spelt out here only)."""
+    return PrefillSegment(slot=slot, row=row, ids=req.prompt_ids, penalty=req.penalty,
+                          temperature=req.temperature, top_p=req.top_p, seed=req.seed,
+                          top_k=req.top_k, min_p=req.min_p, penalty_last_n=req.penalty_last_n,
+                          grammar=bool(req.grammar), pos0=pos0)
+
+
+def check_request(req: StreamRequest, vocab: Optional[int] = None) -> None:
+    """ValueError for what the device would refuse: ``check_params`` of the request and, given
+    ``vocab``, the range of its prompt ids (without it the device checks them)."""
+    kw = request_segment(req, -1, -1).keywords()
+    del kw["seed"], kw["grammar"]  # (nothing to check on the host)
+    check_params(max_tokens=req.max_tokens, **kw)
+    if vocab is not None:
+        ids = np.asarray(req.prompt_ids, dtype=np.int64)
+        if ids.min() < 0 or ids.max() >= vocab:
+            raise ValueError("prompt id out of vocab")
+
+
 class _Row:
     """One stream's decode state; ``idx`` is the device row it decodes in (rows are compacted,
     so it can change), ``slot`` its KV slot (fixed for the stream's life)."""
@@ -167,6 +182,22 @@ class _Row:
         # mid-prompt (a long or prefixed prompt): [positions the slot holds before prompt_ids,
         # the chunks still to enqueue]; the row is reserved and stays parked until the final one
         self.prompt: Optional[list] = None
+
+    def reserve(self, req: StreamRequest, slot: int, n0: int) -> None:
+        """Mid-prompt: the row is taken and stays parked on the device until the final chunk."""
+        self.slot, self.req, self.sched, self.n0 = slot, req, None, n0
+        self.stopped, self.parked = False, True
+
+    def bind(self, req: StreamRequest, slot: int, n0: int, max_pos: int) -> None:
+        """The prompt is on the device: the row decodes from the next step on."""
+        self.slot, self.req, self.sched, self.n0 = slot, req, WindowScheduler(), n0
+        self.limit = max(1, min(req.max_tokens, max_pos - n0))
+        self.issued, self.stopped, self.parked, self.prompt = 1, False, False, None
+
+    def clear(self) -> None:
+        """The stream is gone (ended, cancelled or refused): the row is free."""
+        self.req, self.sched, self.slot, self.prompt = None, None, -1, None
+        self.stopped, self.parked = False, False
 
 
 def plan_compaction(rows: List[_Row]) -> List[Tuple[int, int]]:
@@ -269,6 +300,19 @@ class _Prefix:
         self.pins = 0             # requests in admission that named it
         self.plan: Deque = deque()
         self.handle: Optional[PrefixHandle] = None
+
+
+@dataclass
+class _Admission:
+    """A request on its way into ``row``: its KV slot is taken, its prefix (if any) pinned."""
+    row: _Row
+    req: StreamRequest
+    slot: int
+    n0: int                      # prompt length, the prefix's included
+    prefix: Optional[_Prefix] = None
+
+
+_HOLD = object()  # (admission) the request went back first in line
 
 
 class PrefixRegistry:
@@ -431,7 +475,6 @@ class BatchSynthesizer:
         self._t0 = time.perf_counter()
         self.outstanding_tokens = 0  # tokens still owed to submitted streams (dispatch load)
 
-    # ---------------------------------------------------------------------------------
     def run(self, requests: List[StreamRequest], on_chunk=None) -> float:
         """Serve ``requests`` (admitted in arrival order) to completion; returns wall seconds.
         ``on_chunk(request, pcm_bytes)`` is called for every non-empty PCM chunk in order."""
@@ -439,12 +482,7 @@ class BatchSynthesizer:
         if on_chunk is not None:
             for r in waiting:
                 r.on_chunk = r.on_chunk or on_chunk
-        n = len(waiting)
-        finished = [0]
-
-        def done_cb(_req):
-            finished[0] += 1
-
+        n, done = len(waiting), []   # (done: the requests that have ended)
         t0 = time.perf_counter()
 
         def poll(now):
@@ -457,10 +495,9 @@ class BatchSynthesizer:
             if waiting:
                 time.sleep(max(0.0, min(0.001, waiting[0].arrival - now)))
 
-        self._loop(t0, poll, idle, lambda: finished[0] >= n and not waiting, done_cb)
+        self._loop(t0, poll, idle, lambda: len(done) >= n and not waiting, done.append)
         return time.perf_counter() - t0
 
-    # ---------------------------------------------------------------------------------
     def start(self) -> "BatchSynthesizer":
         """Online mode: a daemon thread owns the GPU and serves ``submit``-ted streams."""
         if self._thread is None:
@@ -471,8 +508,7 @@ class BatchSynthesizer:
         return self
 
     def submit(self, req: StreamRequest) -> StreamHandle:
-        check_params(req.penalty, req.temperature, req.top_p, req.max_tokens, top_k=req.top_k,
-                     min_p=req.min_p, penalty_last_n=req.penalty_last_n)
+        check_request(req)
         check_prefix(req.prefix)
         if self._thread is None:
             self.start()
@@ -572,498 +608,462 @@ class BatchSynthesizer:
                     req.on_done(req)
             raise
 
-    # ---------------------------------------------------------------------------------
     def _loop(self, t0: float, poll, idle, finished, done_cb) -> None:
-        llm, B = self.llm, self.llm.max_batch
-        rows = [_Row(i) for i in range(B)]
-        free_slots = set(range(llm.max_slots - self.prefix_slots))  # (templates sit above)
-        waiting: Deque[StreamRequest] = deque()
-        inflight: Deque = deque()   # (event, [(row, req, k)])
-        pending: Deque = deque()    # (event, ring index, [(req, nbytes)])
-        closing: Deque = deque()    # streams whose end waits for their last SNAC call
-        held: List = []             # due SNAC windows not launched yet (coalescing)
-        held_age = [0]              # decode steps the oldest held window has waited
-        live = self._live
+        _Loop(self, t0, poll, idle, finished, done_cb).run()
 
-        def now():
-            return time.perf_counter() - t0
 
-        def complete(req: StreamRequest) -> None:
-            req.t_done = now()
-            if any(q is req for q in live):
-                live.remove(req)
-            done_cb(req)
-            if req.on_done is not None:
-                req.on_done(req)
+class _Loop:
+    """One run of ``BatchSynthesizer``'s loop: its state, and the steps of ``iterate`` as methods.
+    ``syn`` keeps what outlives a run: engine, streams, staging, prefixes and the counters."""
 
-        def park(r: _Row):
-            if not r.parked:
-                llm.release_row(r.idx, self.stream)
-                r.parked = True
+    def __init__(self, syn: BatchSynthesizer, t0: float, poll, idle, finished, done_cb):
+        self.syn, self.llm, self.stream = syn, syn.llm, syn.stream
+        self.t0, self.poll_fn, self.idle = t0, poll, idle
+        self.finished, self.done_cb = finished, done_cb
+        self.rows = [_Row(i) for i in range(syn.llm.max_batch)]
+        self.free_slots = set(range(syn.llm.max_slots - syn.prefix_slots))  # (templates sit above)
+        self.waiting: Deque[StreamRequest] = deque()
+        self.inflight: Deque = deque()   # (event, [(row, req, k)])
+        self.pending: Deque = deque()    # (event, ring index, [(req, nbytes)])
+        self.closing: Deque = deque()    # streams whose end waits for their last SNAC call
+        self.held: List = []             # due SNAC windows not launched yet (coalescing)
+        self.held_age = 0                # decode steps the oldest held window has waited
 
-        def bind(r: _Row, req: StreamRequest, slot: int, n0: int) -> None:
-            free_slots.discard(slot)
-            r.slot = slot
-            r.req, r.sched, r.n0 = req, WindowScheduler(), n0
-            r.limit = max(1, min(req.max_tokens, llm.max_pos - n0))
-            r.issued, r.stopped, r.parked = 1, False, False
-            req.t_admit = now()
-            if not any(q is req for q in live):
-                live.append(req)
+    def now(self) -> float:
+        return time.perf_counter() - self.t0
 
-        def prefill_one(r: _Row, req: StreamRequest, slot: int, n0: int) -> bool:
-            try:  # a request the device rejects fails alone; the loop serves on
-                check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
-                             top_k=req.top_k, min_p=req.min_p,
-                             penalty_last_n=req.penalty_last_n)
-                llm.prefill(slot, r.idx, req.prompt_ids, req.penalty, self.stream,
-                            temperature=req.temperature, top_p=req.top_p, seed=req.seed,
-                            top_k=req.top_k, min_p=req.min_p,
-                            penalty_last_n=req.penalty_last_n, grammar=bool(req.grammar))
-            except (ValueError, _lib.MxError) as e:
-                if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
-                    raise  # a device failure is not this request's fault
-                req.error = e
-                complete(req)
-                return False
-            bind(r, req, slot, n0)
-            ev = torch.cuda.Event()
-            ev.record(self.stream)
-            inflight.append((ev, [(r, req, 0)]))
-            if r.issued >= r.limit:
-                park(r)
+    def run(self) -> None:
+        while self.iterate():
+            pass
+        for e, _ in self.inflight:
+            e.synchronize()
+
+    def iterate(self) -> bool:
+        """One iteration; False once the driver has finished and nothing is left to serve."""
+        self.poll()
+        self.cancellations()
+        self.control()
+        busy = self.advance_prefixes()
+        self.admit()
+        busy = self.advance_prompts() or busy
+        self.compact()
+        self.issue()
+        stepped = bool(self.inflight)
+        if stepped:
+            self.windows(self.collect())
+        self.drain(block=not stepped and bool(self.pending) and not self.waiting)
+        self.announce()
+        if stepped or self.pending or self.closing or busy:
             return True
+        if self.finished() and not self.waiting and not self.syn._ctl and \
+                all(r.req is None for r in self.rows):
+            return False
+        self.idle(self.now())
+        return True
 
-        def admit_packs(cands: List) -> None:
-            """cands: [(row, request, slot, prompt length, prefix or None)] in admission order,
-            slots already taken out of ``free_slots``, prefixes pinned: per pack of the plan one
-            ``fork_slots`` for its prefixed members, then one ``prefill_batch`` (their suffixes
-            at ``pos0`` = the prefix's length)."""
-            plan = plan_prefill_packs([len(req.prompt_ids) for _, req, _, _, _ in cands],
-                                      llm.max_prefill, B)
+    def poll(self) -> None:
+        self.waiting.extend(self.poll_fn(self.now()))
 
-            def single(r, req, slot, n0, pre) -> None:
-                if pre is None:
-                    if not prefill_one(r, req, slot, n0):
-                        free_slots.add(slot)
+    def complete(self, req: StreamRequest, error: Optional[BaseException] = None) -> None:
+        if error is not None:
+            req.error = error
+        req.t_done = self.now()
+        if any(q is req for q in self.syn._live):
+            self.syn._live.remove(req)
+        self.done_cb(req)
+        if req.on_done is not None:
+            req.on_done(req)
+
+    def park(self, r: _Row) -> None:
+        if not r.parked:
+            self.llm.release_row(r.idx, self.stream)
+            r.parked = True
+
+    def cancellations(self) -> None:
+        for r in self.rows:  # barge-in: free cancelled rows now
+            if r.req is not None and r.req.cancelled:
+                self.finish(r, [])
+
+    def finish(self, r: _Row, due: List) -> None:
+        req = r.req
+        if not req.cancelled and req.audio and r.sched is not None:
+            for win in r.sched.flush():
+                due.append((req, req.windows, win))
+                req.windows += 1
+        self.park(r)
+        self.closing.append(req)
+        self.free_slots.add(r.slot)
+        r.clear()
+
+    def compact(self) -> None:
+        """Live rows to a prefix: a lone stream in row 31 no longer costs a 32-row step."""
+        if self.syn.compact:
+            for dst, src in plan_compaction(self.rows):
+                self.llm.move_row(dst, src, self.stream)
+
+    def refused(self, e: BaseException) -> None:
+        """Only what the device refused for its arguments fails its owner alone."""
+        if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
+            raise e
+
+    def fail(self, a: _Admission, e: BaseException) -> None:
+        if a.row.req is a.req:  # (mid-prompt: the row was reserved)
+            a.row.clear()
+        self.free_slots.add(a.slot)
+        self.complete(a.req, e)
+
+    def enqueued(self, adms: List[_Admission]) -> None:
+        """The prompts of ``adms`` are enqueued: their rows decode on, one event for their tokens."""
+        for a in adms:
+            a.row.bind(a.req, a.slot, a.n0, self.llm.max_pos)
+            a.req.t_admit = self.now()
+            if not any(q is a.req for q in self.syn._live):
+                self.syn._live.append(a.req)
+        ev = torch.cuda.Event()
+        ev.record(self.stream)
+        self.inflight.append((ev, [(a.row, a.req, 0) for a in adms]))
+        for a in adms:
+            if a.row.issued >= a.row.limit:
+                self.park(a.row)
+
+    def control(self) -> None:
+        """Prefix registrations and removals handed to the loop thread."""
+        syn = self.syn
+        while True:
+            with syn._cv:
+                if not syn._ctl:
                     return
-                start_prompt(r, req, slot, pre, n0)
-                if r.req is not req:  # refused on the way
-                    free_slots.add(slot)
-
-            for pack in plan:
-                items = [cands[i] for i in pack]
-                forks = [(slot, pre.slot, pre.n) for _, _, slot, _, pre in items if pre is not None]
-                try:
-                    if 0 < len(forks) < PREFIX_PACK_MIN:
-                        # too few for the pack to pay: they take the chunked path as ever
-                        for it in items:
-                            if it[4] is not None:
-                                single(*it)
-                        items = [it for it in items if it[4] is None]
-                        forks = []
-                        if not items:
-                            continue
-                    segs = [PrefillSegment(
-                        slot=slot, row=r.idx, ids=req.prompt_ids, penalty=req.penalty,
-                        temperature=req.temperature, top_p=req.top_p, seed=req.seed,
-                        top_k=req.top_k, min_p=req.min_p, penalty_last_n=req.penalty_last_n,
-                        grammar=bool(req.grammar), pos0=pre.n if pre is not None else 0)
-                        for r, req, slot, _, pre in items]
-                    try:
-                        if forks:
-                            llm.fork_slots(forks, self.stream)
-                        llm.prefill_batch(segs, self.stream)
-                    except _lib.MxError as e:
-                        if e.rc not in (_lib.MX_ERR_ARG, _lib.MX_ERR_STATE):
-                            raise
-                        # refused as a whole (no prefill was enqueued): request by request, so
-                        # the bad one fails alone
-                        for it in items:
-                            single(*it)
-                        continue
-                finally:
-                    for i in pack:
-                        if cands[i][4] is not None:
-                            cands[i][4].pins -= 1
-                self.prefill_packs[len(items)] += 1
-                if forks:
-                    self.prefix_packs[len(items)] += 1
-                for r, req, slot, n0, pre in items:
-                    if pre is not None:
-                        self.prefix_forks[pre.name] += 1
-                    bind(r, req, slot, n0)
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-                inflight.append((ev, [(r, req, 0) for r, req, _, _, _ in items]))
-                for r, _, _, _, _ in items:
-                    if r.issued >= r.limit:
-                        park(r)
-
-        def refused(e) -> bool:
-            """A chunk or fork the device refused for its arguments fails its owner alone."""
-            if isinstance(e, _lib.MxError) and e.rc != _lib.MX_ERR_ARG:
-                raise e  # a device failure is nobody's fault
-            return True
-
-        def control() -> None:
-            """Prefix registrations and removals handed to the loop thread."""
-            while True:
-                with self._cv:
-                    if not self._ctl:
-                        return
-                    op, name, ids, h = self._ctl.popleft()
-                    p, old, err = None, None, None
-                    if op == "unregister":
-                        p = self.prefixes.remove(name)
-                    else:  # (under the lock: has_prefix never sees the name in neither place)
-                        try:
-                            p, old = self.prefixes.place(name, ids)
-                        except RuntimeError as e:
-                            err = e
-                            if any(not q.ready for q in self.prefixes.entries.values()):
-                                # a slot frees up once the prefix being prefilled is ready
-                                self._ctl.appendleft((op, name, ids, h))
-                                return
+                op, name, ids, h = syn._ctl.popleft()
+                p, old, err = None, None, None
                 if op == "unregister":
-                    if p is not None and p.handle is not None and not p.handle.done:
-                        p.handle._finish(KeyError(f"prefix {name!r} was unregistered"))
-                    h._finish(None if p is not None else KeyError(f"unknown prefix {name!r}"))
-                    continue
-                if err is not None:
-                    h._finish(err)
-                    continue
-                if old is not None and old.handle is not None and not old.handle.done:
-                    old.handle._finish(KeyError(f"prefix {old.name!r} was replaced"))
-                p.handle = h
-                p.plan = deque(plan_prompt_chunks(p.n, 0, llm.max_prefill))
-
-        def advance_prefixes() -> bool:
-            """One chunk of every prefix still being prefilled; True while one is unfinished."""
-            busy = False
-            for p in [q for q in self.prefixes.entries.values() if not q.ready]:
-                off, n, _ = p.plan.popleft()
-                try:  # every chunk of a template is non-final: layers and KV only
-                    llm.prefill_chunk(p.slot, p.ids[off:off + n], off, self.stream)
-                except (ValueError, _lib.MxError) as e:
-                    refused(e)
-                    self.prefixes.remove(p.name)
-                    p.handle._finish(e)
-                    continue
-                self.prompt_chunks += 1
-                if p.plan:
-                    busy = True
-                    continue
-                p.ready = True
-                self.prefix_fills[p.name] += 1
-                p.handle._finish(None)
-            return busy
-
-        def drop_prompt(r: _Row, e: BaseException) -> None:
-            req = r.req
-            free_slots.add(r.slot)
-            r.req, r.sched, r.stopped, r.parked, r.slot, r.prompt = None, None, False, False, -1, None
-            req.error = e
-            complete(req)
-
-        def start_prompt(r: _Row, req: StreamRequest, slot: int, pre: Optional[_Prefix],
-                         n0: int) -> None:
-            """Reserve row and slot for a prompt that is not one plain prefill: the fork of its
-            prefix now, its chunks from ``advance_prompts`` on."""
-            try:
-                check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
-                             top_k=req.top_k, min_p=req.min_p,
-                             penalty_last_n=req.penalty_last_n)
-                ids = np.asarray(req.prompt_ids, dtype=np.int64)
-                if ids.min() < 0 or ids.max() >= llm.cfg.vocab:
-                    raise ValueError("prompt id out of vocab")
-            except ValueError as e:
-                req.error = e
-                complete(req)
-                return
-            free_slots.discard(slot)
-            r.slot, r.req, r.sched, r.n0 = slot, req, None, n0
-            r.stopped, r.parked = False, True   # parked on the device until the final chunk
-            live.append(req)
-            pos0 = 0
-            if pre is not None:
-                pre.pins += 1
-                try:
-                    llm.fork_slot(slot, pre.slot, pre.n, self.stream)
-                except _lib.MxError as e:
-                    refused(e)
-                    drop_prompt(r, e)
-                    return
-                finally:
-                    pre.pins -= 1
-                self.prefix_forks[pre.name] += 1
-                pos0 = pre.n
-            r.prompt = [pos0, deque(plan_prompt_chunks(len(req.prompt_ids), pos0, llm.max_prefill))]
-
-        def advance_prompts() -> bool:
-            """Every mid-prompt row: its next chunks up to and including ONE non-final chunk (the
-            live streams step between chunks); the final chunk binds the row as prefill_one
-            does.  True while a row is still mid-prompt."""
-            busy = False
-            for r in rows:
-                if r.req is None or r.prompt is None:
-                    continue
-                req = r.req
-                pos0, plan = r.prompt
-                last = False
-                while plan and not last:
-                    off, n, last = plan.popleft()
-                    kw = dict(last=True, row=r.idx, penalty=req.penalty,
-                              temperature=req.temperature, top_p=req.top_p, seed=req.seed,
-                              top_k=req.top_k, min_p=req.min_p,
-                              penalty_last_n=req.penalty_last_n,
-                              grammar=bool(req.grammar)) if last else {}
+                    p = syn.prefixes.remove(name)
+                else:  # (under the lock: has_prefix never sees the name in neither place)
                     try:
-                        llm.prefill_chunk(r.slot, req.prompt_ids[off:off + n], pos0 + off,
-                                          self.stream, **kw)
-                    except (ValueError, _lib.MxError) as e:
-                        refused(e)
-                        drop_prompt(r, e)
-                        break
-                    self.prompt_chunks += 1
-                    if not last:
-                        break
-                if r.req is not req:
-                    continue
-                if not last:
-                    busy = True
-                    continue
-                r.prompt = None
-                bind(r, req, r.slot, r.n0)
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-                inflight.append((ev, [(r, req, 0)]))
-                if r.issued >= r.limit:
-                    park(r)
-            return busy
+                        p, old = syn.prefixes.place(name, ids)
+                    except RuntimeError as e:
+                        err = e
+                        if any(not q.ready for q in syn.prefixes.entries.values()):
+                            # a slot frees up once the prefix being prefilled is ready
+                            syn._ctl.appendleft((op, name, ids, h))
+                            return
+            if op == "unregister":
+                if p is not None and p.handle is not None and not p.handle.done:
+                    p.handle._finish(KeyError(f"prefix {name!r} was unregistered"))
+                h._finish(None if p is not None else KeyError(f"unknown prefix {name!r}"))
+                continue
+            if err is not None:
+                h._finish(err)
+                continue
+            if old is not None and old.handle is not None and not old.handle.done:
+                old.handle._finish(KeyError(f"prefix {old.name!r} was replaced"))
+            p.handle = h
+            p.plan = deque(plan_prompt_chunks(p.n, 0, self.llm.max_prefill))
 
-        def admit():
-            cands: List = []  # packed prefill: the requests this iteration admits
-            for r in rows:
-                if not waiting:
+    def advance_prefixes(self) -> bool:
+        """One chunk of every prefix still being prefilled; True while one is unfinished."""
+        syn, busy = self.syn, False
+        for p in [q for q in syn.prefixes.entries.values() if not q.ready]:
+            off, n, _ = p.plan.popleft()
+            try:  # every chunk of a template is non-final: layers and KV only
+                self.llm.prefill_chunk(p.slot, p.ids[off:off + n], off, self.stream)
+            except (ValueError, _lib.MxError) as e:
+                self.refused(e)
+                syn.prefixes.remove(p.name)
+                p.handle._finish(e)
+                continue
+            syn.prompt_chunks += 1
+            if p.plan:
+                busy = True
+                continue
+            p.ready = True
+            syn.prefix_fills[p.name] += 1
+            p.handle._finish(None)
+        return busy
+
+    def admit(self) -> None:
+        """Waiting requests into the free rows, one per row, each validated on the host (the plain
+        unpacked path leaves its ids to the device).  Those that fit a pack wait for
+        ``admit_packs``; a prefix stays pinned until the iteration's forks are enqueued."""
+        llm, formed, cands = self.llm, [], []
+        try:
+            for r in self.rows:
+                if not self.waiting:
                     break
                 if r.req is not None:
                     continue
-                req = waiting.popleft()
-                if req.cancelled:
-                    complete(req)
+                a = self.candidate(r, idle=not cands and all(q.req is None for q in self.rows))
+                if a is _HOLD:
+                    break
+                if a is None:
                     continue
-                pre = None
-                if req.prefix is not None:
-                    pre = self.prefixes.get(req.prefix) if isinstance(req.prefix, str) else None
-                    if pre is None and isinstance(req.prefix, str) and self.has_prefix(req.prefix):
-                        waiting.appendleft(req)  # its registration has not reached the loop yet
-                        break
-                    if pre is None:  # an unknown (or evicted) name fails this request alone
-                        req.error = UnknownPrefix(f"unknown prefix {req.prefix!r}")
-                        complete(req)
-                        continue
-                    if not pre.ready:  # still being prefilled: first in line, holds later arrivals
-                        waiting.appendleft(req)
-                        break
-                # n0, limit, the window scheduler and the grammar count from the whole prompt
-                n0 = len(req.prompt_ids) + (pre.n if pre is not None else 0)
-                if len(req.prompt_ids) < 1 or n0 >= llm.max_pos:
-                    req.error = ValueError(f"prompt of {n0} ids does not fit (max_pos "
-                                           f"{llm.max_pos})")
-                    complete(req)
-                    continue
-                # packed prefill takes the prompts that fit one chunk and, behind a ready prefix,
-                # the suffixes that do; everything longer goes chunk by chunk
-                chunked = n0 > llm.max_prefill if pre is None else \
-                    not (self.packed_prefill and len(req.prompt_ids) <= llm.max_prefill)
-                if req.grammar and llm.grammar is None:
-                    # the context takes its grammar while idle: the first constrained request
-                    # waits for the live streams (and, first in line, holds later arrivals)
-                    if cands or any(q.req is not None for q in rows):
-                        waiting.appendleft(req)
-                        break
-                    for q in rows:
-                        park(q)
-                    try:  # a vocabulary that cannot hold the preset fails this request alone
-                        llm.set_grammar(ORPHEUS_GRAMMAR)
-                    except _lib.MxError as e:
-                        if e.rc != _lib.MX_ERR_ARG:
-                            raise
-                        req.error = e
-                        complete(req)
-                        continue
-                if req.noise_seed is None:
-                    req.noise_seed = (self.seed * 1000003 + self._admitted) & _MASK48
-                self._admitted += 1
-                slot = min(free_slots)
-                if chunked:
-                    start_prompt(r, req, slot, pre, n0)
-                    continue
-                if not self.packed_prefill:
-                    prefill_one(r, req, slot, n0)
-                    continue
-                try:  # what the device would refuse is refused here, before the pack forms
-                    check_params(req.penalty, req.temperature, req.top_p, req.max_tokens,
-                                 top_k=req.top_k, min_p=req.min_p,
-                                 penalty_last_n=req.penalty_last_n)
-                    ids = np.asarray(req.prompt_ids, dtype=np.int64)
-                    if ids.min() < 0 or ids.max() >= llm.cfg.vocab:
-                        raise ValueError("prompt id out of vocab")
+                formed.append(a)
+                # a pack takes the prompts that fit one chunk and, behind a ready prefix, the
+                # suffixes that do; everything longer goes chunk by chunk
+                pack = self.syn.packed_prefill and len(a.req.prompt_ids) <= llm.max_prefill
+                try:
+                    check_request(a.req, llm.cfg.vocab if pack or self.chunked(a) else None)
                 except ValueError as e:
-                    req.error = e
-                    complete(req)
+                    self.fail(a, e)
                     continue
-                free_slots.discard(slot)
-                if pre is not None:
-                    pre.pins += 1  # (not evicted before its fork is enqueued: admit_packs)
-                cands.append((r, req, slot, n0, pre))
-            if cands:
-                admit_packs(cands)
+                if pack:
+                    cands.append(a)
+                else:
+                    self.single(a)
+            self.admit_packs(cands)
+        finally:
+            for a in formed:
+                if a.prefix is not None:
+                    a.prefix.pins -= 1
 
-        def launch_windows(due: List):
-            """due: [(req, window index, codes)] -> one SNAC call per frame-count group."""
-            groups: Dict[int, List] = {}
-            for item in due:  # grouped by the frames the kept slice depends on (7 -> 5)
-                n = len(item[2]) // 7
-                groups.setdefault(frames_for_slice(n, min(SLICE_HI, SAMPLES_PER_FRAME * n)),
-                                  []).append(item)
-            for nf, items in groups.items():
-                for s in range(0, len(items), self.ring.max_batch):
-                    chunk = items[s:s + self.ring.max_batch]
-                    i = self._calls % self.ring.n
-                    while len(pending) >= self.ring.n:
-                        drain(block=True, upto=1)
-                    codes, seeds = self.ring.codes[i], self.ring.seeds[i]
-                    for j, (req, widx, win) in enumerate(chunk):
-                        codes[j * 7 * nf:(j + 1) * 7 * nf] = win[:7 * nf]
-                        seeds[j] = window_seed(req.noise_seed, widx)
-                    lo, hi = SLICE_LO, min(SLICE_HI, SAMPLES_PER_FRAME * nf)
-                    hi = max(lo, hi)
-                    self.snac.decode_ptr(self.ring.codes_dev[i], nf, len(chunk), 0, 0,
-                                         self.ring.pcm_dev[i] if hi > lo else 0, 0, lo, hi,
-                                         self.snac_stream, seeds_ptr=self.ring.seeds_dev[i])
-                    e = torch.cuda.Event()
-                    e.record(self.snac_stream)
-                    pending.append((e, i, [(req, (hi - lo) * 2) for req, _, _ in chunk]))
-                    self._calls += 1
+    def candidate(self, r: _Row, idle: bool):
+        """The next waiting request as a candidate for row ``r`` (slot taken, prefix pinned);
+        None when it ended here, ``_HOLD`` when it went back first in line, where it holds
+        later arrivals.  ``idle``: no stream is live and none was formed in this iteration."""
+        syn, llm = self.syn, self.llm
+        req = self.waiting.popleft()
+        if req.cancelled:
+            return self.complete(req)
+        pre = None
+        if req.prefix is not None:
+            named = isinstance(req.prefix, str)
+            pre = syn.prefixes.get(req.prefix) if named else None
+            # still being prefilled, or its registration has not reached the loop yet
+            coming = named and syn.has_prefix(req.prefix) if pre is None else not pre.ready
+            if coming:
+                self.waiting.appendleft(req)
+                return _HOLD
+            if pre is None:  # an unknown (or evicted) name fails this request alone
+                return self.complete(req, UnknownPrefix(f"unknown prefix {req.prefix!r}"))
+        # n0, limit, the window scheduler and the grammar count from the whole prompt
+        n0 = len(req.prompt_ids) + (pre.n if pre is not None else 0)
+        if len(req.prompt_ids) < 1 or n0 >= llm.max_pos:
+            return self.complete(req, ValueError(f"prompt of {n0} ids does not fit (max_pos "
+                                                 f"{llm.max_pos})"))
+        if req.grammar and llm.grammar is None:
+            if not idle:  # the context takes its grammar while idle: wait for the live streams
+                self.waiting.appendleft(req)
+                return _HOLD
+            for q in self.rows:
+                self.park(q)
+            try:  # a vocabulary that cannot hold the preset fails this request alone
+                llm.set_grammar(ORPHEUS_GRAMMAR)
+            except _lib.MxError as e:
+                self.refused(e)
+                return self.complete(req, e)
+        if req.noise_seed is None:
+            req.noise_seed = window_seed(syn.seed, syn._admitted)
+        syn._admitted += 1
+        slot = min(self.free_slots)
+        self.free_slots.discard(slot)
+        if pre is not None:
+            pre.pins += 1
+        return _Admission(r, req, slot, n0, pre)
 
-        def drain(block: bool, upto: Optional[int] = None):
-            k = 0
-            while pending and (upto is None or k < upto):
-                e, i, items = pending[0]
-                if not block and not e.query():
-                    return
-                e.synchronize()
-                pending.popleft()
-                k += 1
-                pcm = self.ring.pcm[i]
-                for j, (req, nbytes) in enumerate(items):
-                    if not nbytes or req.cancelled:
-                        continue
-                    n = nbytes // 2
-                    data = pcm[j * n:(j + 1) * n].tobytes()
-                    req.samples += n
-                    if req.t_first_audio is None:
-                        req.t_first_audio = now()
-                    if req.on_chunk is not None:
-                        req.on_chunk(req, data)
+    def chunked(self, a: _Admission) -> bool:
+        return a.prefix is not None or a.n0 > self.llm.max_prefill
 
-        def finish(r: _Row, due: List):
-            req = r.req
-            if not req.cancelled and req.audio and r.sched is not None:
-                for win in r.sched.flush():
+    def single(self, a: _Admission) -> None:
+        """Admit ``a`` alone: a prefixed or long prompt chunk by chunk, any other by one prefill."""
+        if self.chunked(a):
+            return self.start_prompt(a)
+        try:  # a request the device rejects fails alone; the loop serves on
+            seg = request_segment(a.req, a.slot, a.row.idx)
+            self.llm.prefill(seg.slot, seg.row, seg.ids, stream=self.stream, **seg.keywords())
+        except (ValueError, _lib.MxError) as e:
+            self.refused(e)
+            return self.fail(a, e)
+        self.enqueued([a])
+
+    def admit_packs(self, cands: List[_Admission]) -> None:
+        """``cands`` in admission order: per pack of the plan one ``fork_slots`` for its prefixed
+        members, then one ``prefill_batch`` (their suffixes at ``pos0`` = the prefix's length)."""
+        syn, llm = self.syn, self.llm
+        plan = plan_prefill_packs([len(a.req.prompt_ids) for a in cands], llm.max_prefill,
+                                  llm.max_batch)
+        for pack in plan:
+            items = [cands[i] for i in pack]
+            prefixed = [a for a in items if a.prefix is not None]
+            if 0 < len(prefixed) < PREFIX_PACK_MIN:
+                # too few for the pack to pay: they take the chunked path as ever
+                for a in prefixed:
+                    self.single(a)
+                items, prefixed = [a for a in items if a.prefix is None], []
+                if not items:
+                    continue
+            segs = [request_segment(a.req, a.slot, a.row.idx,
+                                    pos0=a.prefix.n if a.prefix is not None else 0) for a in items]
+            try:
+                if prefixed:
+                    llm.fork_slots([(a.slot, a.prefix.slot, a.prefix.n) for a in prefixed],
+                                   self.stream)
+                llm.prefill_batch(segs, self.stream)
+            except _lib.MxError as e:
+                if e.rc not in (_lib.MX_ERR_ARG, _lib.MX_ERR_STATE):
+                    raise
+                for a in items:  # refused as a whole, nothing enqueued: the bad one fails alone
+                    self.single(a)
+                continue
+            syn.prefill_packs[len(items)] += 1
+            if prefixed:
+                syn.prefix_packs[len(items)] += 1
+            for a in prefixed:
+                syn.prefix_forks[a.prefix.name] += 1
+            self.enqueued(items)
+
+    def start_prompt(self, a: _Admission) -> None:
+        """Reserve the row for a long or prefixed prompt: the fork of its prefix now, its chunks
+        from ``advance_prompts`` on."""
+        r, req, pre = a.row, a.req, a.prefix
+        r.reserve(req, a.slot, a.n0)
+        self.syn._live.append(req)
+        pos0 = 0
+        if pre is not None:
+            try:
+                self.llm.fork_slot(a.slot, pre.slot, pre.n, self.stream)
+            except _lib.MxError as e:
+                self.refused(e)
+                return self.fail(a, e)
+            self.syn.prefix_forks[pre.name] += 1
+            pos0 = pre.n
+        r.prompt = [pos0, deque(plan_prompt_chunks(len(req.prompt_ids), pos0,
+                                                   self.llm.max_prefill))]
+
+    def advance_prompts(self) -> bool:
+        """Every mid-prompt row one step on; True while a row is still mid-prompt."""
+        return any([self.advance_prompt(r) for r in self.rows  # (a list: every row advances)
+                    if r.req is not None and r.prompt is not None])
+
+    def advance_prompt(self, r: _Row) -> bool:
+        """``r``'s next chunks up to and including ONE non-final chunk (the live streams step
+        between chunks); the final chunk binds the row as a plain prefill does.  True while the
+        row is still mid-prompt."""
+        a, (pos0, plan), last = _Admission(r, r.req, r.slot, r.n0), r.prompt, False
+        while not last:
+            off, n, last = plan.popleft()
+            kw = dict(request_segment(a.req, r.slot, r.idx).keywords(), last=True, row=r.idx) \
+                if last else {}
+            try:
+                self.llm.prefill_chunk(r.slot, a.req.prompt_ids[off:off + n], pos0 + off,
+                                       self.stream, **kw)
+            except (ValueError, _lib.MxError) as e:
+                self.refused(e)
+                self.fail(a, e)
+                return False
+            self.syn.prompt_chunks += 1
+            if not last:
+                return True
+        self.enqueued([a])
+        return False
+
+    def issue(self) -> None:
+        """Keep ``depth`` steps queued for the rows that still need tokens."""
+        act = [r for r in self.rows if r.req is not None and not r.stopped and not r.parked]
+        while act and len(self.inflight) < self.syn.depth:
+            n_rows = max(r.idx for r in act) + 1
+            self.llm.decode(n_rows, self.stream)
+            self.syn.row_steps[n_rows] += 1
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+            entries = [(r, r.req, r.issued) for r in act]
+            for r in act:
+                r.issued += 1
+                if r.issued >= r.limit:
+                    self.park(r)
+            self.inflight.append((ev, entries))
+            act = [r for r in act if not r.parked]
+
+    def collect(self) -> List:
+        """The oldest queued step's tokens, read from the history; streams that ended free their
+        rows.  Returns the SNAC windows that fell due: [(req, window index, codes)]."""
+        ev, entries = self.inflight.popleft()
+        ev.synchronize()
+        self.llm.check(self.stream)
+        due: List = []
+        for r, req, k in entries:
+            if r.req is not req or r.stopped or req.cancelled:
+                continue  # speculative step of a stream that already ended
+            tok = int(self.llm.hist[r.slot, r.n0 + k])
+            req.tokens.append(tok)
+            if req.on_token is not None:
+                req.on_token(req, tok)
+            if req.audio:
+                feed = int(req.inject_ids[k]) if req.inject_ids is not None else tok
+                for win in r.sched.push(code_of_id(feed, r.sched.count)):
                     due.append((req, req.windows, win))
                     req.windows += 1
-            park(r)
-            closing.append(req)
-            free_slots.add(r.slot)
-            r.req, r.sched, r.stopped, r.parked, r.slot = None, None, False, False, -1
-            r.prompt = None
+            if tok in req.stop_ids or len(req.tokens) >= r.limit:
+                r.stopped = True
+        for r in self.rows:
+            if r.req is not None and r.stopped:
+                self.finish(r, due)
+        return due
 
-        def compact():
-            """Live rows to a prefix (plan_compaction), so a step runs the row class of the
-            live stream count: a lone stream in row 31 no longer costs a 32-row step."""
-            if not self.compact:
+    def windows(self, due: List) -> None:
+        """Coalescing: hold the due windows until enough are ready or the oldest has waited."""
+        syn, held = self.syn, self.held
+        if held:
+            self.held_age += 1
+        held.extend(due)
+        if held and (len(held) >= syn.snac_min_batch or self.held_age >= syn.snac_max_hold or
+                     self.closing or any(w == 0 for _, w, _ in held) or not self.inflight):
+            self.launch_windows(held)
+            held.clear()
+            self.held_age = 0
+
+    def launch_windows(self, due: List) -> None:
+        """due: [(req, window index, codes)] -> one SNAC call per frame-count group."""
+        syn, ring = self.syn, self.syn.ring
+        groups: Dict[int, List] = {}
+        for item in due:  # grouped by the frames the kept slice depends on (7 -> 5)
+            n = len(item[2]) // 7
+            groups.setdefault(frames_for_slice(n, min(SLICE_HI, SAMPLES_PER_FRAME * n)),
+                              []).append(item)
+        for nf, items in groups.items():
+            for s in range(0, len(items), ring.max_batch):
+                chunk = items[s:s + ring.max_batch]
+                i = syn._calls % ring.n
+                while len(self.pending) >= ring.n:
+                    self.drain(block=True, upto=1)
+                codes, seeds = ring.codes[i], ring.seeds[i]
+                for j, (req, widx, win) in enumerate(chunk):
+                    codes[j * 7 * nf:(j + 1) * 7 * nf] = win[:7 * nf]
+                    seeds[j] = window_seed(req.noise_seed, widx)
+                lo, hi = SLICE_LO, max(SLICE_LO, min(SLICE_HI, SAMPLES_PER_FRAME * nf))
+                syn.snac.decode_ptr(ring.codes_dev[i], nf, len(chunk), 0, 0,
+                                    ring.pcm_dev[i] if hi > lo else 0, 0, lo, hi,
+                                    syn.snac_stream, seeds_ptr=ring.seeds_dev[i])
+                e = torch.cuda.Event()
+                e.record(syn.snac_stream)
+                self.pending.append((e, i, [(req, (hi - lo) * 2) for req, _, _ in chunk]))
+                syn._calls += 1
+
+    def drain(self, block: bool, upto: Optional[int] = None) -> None:
+        k = 0
+        while self.pending and (upto is None or k < upto):
+            e, i, items = self.pending[0]
+            if not block and not e.query():
                 return
-            for dst, src in plan_compaction(rows):
-                llm.move_row(dst, src, self.stream)
-
-        def announce():
-            # a closing stream's windows were all launched when it closed: once no pending
-            # SNAC call holds one of them, its end is announced (in close order)
-            while closing:
-                req = closing[0]
-                if any(q is req for _, _, items in pending for q, _ in items):
-                    return
-                closing.popleft()
-                complete(req)
-
-        while True:
-            waiting.extend(poll(now()))
-            for r in rows:  # barge-in: free cancelled rows now
-                if r.req is not None and r.req.cancelled:
-                    finish(r, [])
-            control()
-            busy = advance_prefixes()
-            admit()
-            busy = advance_prompts() or busy
-            compact()
-            act = [r for r in rows if r.req is not None and not r.stopped and not r.parked]
-            # keep `depth` steps queued for the rows that still need tokens
-            while act and len(inflight) < self.depth:
-                n_rows = max(r.idx for r in act) + 1
-                llm.decode(n_rows, self.stream)
-                self.row_steps[n_rows] += 1
-                ev = torch.cuda.Event()
-                ev.record(self.stream)
-                entries = []
-                for r in act:
-                    entries.append((r, r.req, r.issued))
-                    r.issued += 1
-                    if r.issued >= r.limit:
-                        park(r)
-                inflight.append((ev, entries))
-                act = [r for r in act if not r.parked]
-            if not inflight:
-                drain(block=bool(pending) and not waiting)
-                announce()
-                if finished() and not pending and not closing and not waiting and \
-                        not busy and not self._ctl and all(r.req is None for r in rows):
-                    break
-                if not pending and not closing and not busy:
-                    idle(now())
-                continue
-            ev, entries = inflight.popleft()
-            ev.synchronize()
-            llm.check(self.stream)
-            due: List = []
-            for r, req, k in entries:
-                if r.req is not req or r.stopped or req.cancelled:
-                    continue  # speculative step of a stream that already ended
-                tok = int(llm.hist[r.slot, r.n0 + k])
-                req.tokens.append(tok)
-                if req.on_token is not None:
-                    req.on_token(req, tok)
-                if req.audio:
-                    feed = int(req.inject_ids[k]) if req.inject_ids is not None else tok
-                    for win in r.sched.push(code_of_id(feed, r.sched.count)):
-                        due.append((req, req.windows, win))
-                        req.windows += 1
-                if tok in req.stop_ids or len(req.tokens) >= r.limit:
-                    r.stopped = True
-            for r in rows:
-                if r.req is not None and r.stopped:
-                    finish(r, due)
-            if held:
-                held_age[0] += 1
-            held.extend(due)
-            if held and (len(held) >= self.snac_min_batch or held_age[0] >= self.snac_max_hold or
-                         closing or any(w == 0 for _, w, _ in held) or not inflight):
-                launch_windows(held)
-                held.clear()
-                held_age[0] = 0
-            drain(block=False)
-            announce()
-        for e, _ in inflight:
             e.synchronize()
+            self.pending.popleft()
+            k += 1
+            pcm = self.syn.ring.pcm[i]
+            for j, (req, nbytes) in enumerate(items):
+                if not nbytes or req.cancelled:
+                    continue
+                n = nbytes // 2
+                data = pcm[j * n:(j + 1) * n].tobytes()
+                req.samples += n
+                if req.t_first_audio is None:
+                    req.t_first_audio = self.now()
+                if req.on_chunk is not None:
+                    req.on_chunk(req, data)
+
+    def announce(self) -> None:
+        """A closing stream's windows were all launched when it closed: once no pending SNAC call
+        holds one of them, its end is announced (in close order)."""
+        while self.closing:
+            req = self.closing[0]
+            if any(q is req for _, _, items in self.pending for q, _ in items):
+                return
+            self.closing.popleft()
+            self.complete(req)

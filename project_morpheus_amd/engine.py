@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import time
 from collections import deque
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 from typing import Callable, Dict, Iterator, List, Optional, Sequence
 
 import numpy as np
@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from .config import (ENGINE_OPTIONS, ORPHEUS_GRAMMAR, STOP_IDS, OrpheusConfig, grammar_default,
                      rope_tables)
-from .schedule import WindowScheduler, code_of_id, frames_for_slice
+from .schedule import WindowScheduler, code_of_id, frames_for_slice, window_seed
 
 SAMPLES_PER_FRAME = 2048
 SLICE_LO, SLICE_HI = 2048, 4096
@@ -59,6 +59,11 @@ class PrefillSegment:
     penalty_last_n: int = 0
     grammar: bool = False
     pos0: int = 0
+
+    def keywords(self) -> dict:
+        """The generation parameters by name: ``prefill``'s and a final chunk's keywords."""
+        return {f.name: getattr(self, f.name) for f in fields(self)
+                if f.name not in ("slot", "row", "ids", "pos0")}
 
 
 class LlmEngine:
@@ -106,6 +111,32 @@ class LlmEngine:
     def _check(self, rc):
         _lib.check(rc, self.lib.mx_llm_last_error, self.h)
 
+    def _sync_slot_grammar(self, slot: int, grammar: bool) -> None:
+        """``slot``'s constrained flag up to date (one out of range: the prefill refuses it)."""
+        if bool(grammar) != self._slot_grammar.get(slot, False) and 0 <= slot < self.max_slots:
+            self._check(self.lib.mx_llm_set_slot_grammar(self.h, slot, int(bool(grammar))))
+            self._slot_grammar[slot] = bool(grammar)
+
+    def _sampling(self, s: PrefillSegment):
+        """A segment's generation parameters as the C ABI's (mx_sampling, mx_sampling_ext)."""
+        return (_lib.Sampling(temperature=float(s.temperature), top_p=float(s.top_p),
+                              repetition_penalty=float(s.penalty), seed=int(s.seed) & (2**64 - 1)),
+                _lib.SamplingExt(top_k=int(s.top_k), min_p=float(s.min_p),
+                                 penalty_last_n=int(s.penalty_last_n)))
+
+    def _fill(self, a, s: PrefillSegment, last: bool = True) -> np.ndarray:
+        """Segment ``s`` into ``a`` (a ``_lib.PrefillSeg`` / ``PrefillChunk``); ``last``: the prompt
+        ends here, the slot takes its parameters.  Returns the id array ``a`` points into."""
+        if last:
+            self._sync_slot_grammar(s.slot, s.grammar)
+        ids = np.ascontiguousarray(np.asarray(s.ids, dtype=np.int32))
+        a.slot, a.row, a.ids_host, a.n_ids = int(s.slot), int(s.row), ids.ctypes.data, len(ids)
+        if isinstance(a, _lib.PrefillChunk):
+            a.pos0, a.last = int(s.pos0), int(last)
+        if last:
+            a.params, a.ext = self._sampling(s)
+        return ids
+
     def prefill(self, slot: int, row: int, ids: Sequence[int], penalty: float, stream, *,
                 temperature: float = 0.0, top_p: float = 1.0, seed: int = 0,
                 top_k: int = 0, min_p: float = 0.0, penalty_last_n: int = 0,
@@ -116,16 +147,11 @@ class LlmEngine:
         penalises the ids of the last N positions only (0 = the whole sequence, N <= 255).
         ``grammar``: the stream picks from the allowed ids of the engine's code grammar only
         (``set_grammar`` first)."""
-        if bool(grammar) != self._slot_grammar.get(slot, False):
-            self._check(self.lib.mx_llm_set_slot_grammar(self.h, slot, int(bool(grammar))))
-            self._slot_grammar[slot] = bool(grammar)
-        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
-        sp = _lib.Sampling(temperature=float(temperature), top_p=float(top_p),
-                           repetition_penalty=float(penalty), seed=int(seed) & (2**64 - 1))
-        ext = _lib.SamplingExt(top_k=int(top_k), min_p=float(min_p),
-                               penalty_last_n=int(penalty_last_n))
-        self._check(self.lib.mx_llm_prefill_ex(self.h, slot, row, arr.ctypes.data, len(arr),
-                                               C.byref(sp), C.byref(ext),
+        a = _lib.PrefillSeg()
+        keep = self._fill(a, PrefillSegment(slot, row, ids, penalty, temperature, top_p, seed,
+                                            top_k, min_p, penalty_last_n, grammar))
+        self._check(self.lib.mx_llm_prefill_ex(self.h, slot, row, a.ids_host, a.n_ids,
+                                               C.byref(a.params), C.byref(a.ext),
                                                C.c_void_p(stream.cuda_stream)))
 
     def prefill_batch(self, segments: Sequence, stream) -> None:
@@ -136,26 +162,10 @@ class LlmEngine:
         with ``pos0 > 0`` continue their slots (mx_llm_prefill_pack: the state the same final
         ``prefill_chunk`` calls in order would leave)."""
         segs = [s if isinstance(s, PrefillSegment) else PrefillSegment(**s) for s in segments]
-        for s in segs:
-            if bool(s.grammar) != self._slot_grammar.get(s.slot, False) and \
-                    0 <= s.slot < self.max_slots:
-                self._check(self.lib.mx_llm_set_slot_grammar(self.h, s.slot, int(bool(s.grammar))))
-                self._slot_grammar[s.slot] = bool(s.grammar)
         # behind a history the pack of final chunks; every pos0 = 0: the packed prefill as ever
         pack = any(int(s.pos0) != 0 for s in segs)
         arr = ((_lib.PrefillChunk if pack else _lib.PrefillSeg) * max(1, len(segs)))()
-        keep = []  # the id arrays live until the call returns
-        for a, s in zip(arr, segs):
-            ids = np.ascontiguousarray(np.asarray(s.ids, dtype=np.int32))
-            keep.append(ids)
-            a.slot, a.row, a.ids_host, a.n_ids = int(s.slot), int(s.row), ids.ctypes.data, len(ids)
-            if pack:
-                a.pos0, a.last = int(s.pos0), 1
-            a.params = _lib.Sampling(temperature=float(s.temperature), top_p=float(s.top_p),
-                                     repetition_penalty=float(s.penalty),
-                                     seed=int(s.seed) & (2**64 - 1))
-            a.ext = _lib.SamplingExt(top_k=int(s.top_k), min_p=float(s.min_p),
-                                     penalty_last_n=int(s.penalty_last_n))
+        keep = [self._fill(a, s) for a, s in zip(arr, segs)]  # (alive until the call returns)
         call = self.lib.mx_llm_prefill_pack if pack else self.lib.mx_llm_prefill_batch
         self._check(call(self.h, arr, len(segs), C.c_void_p(stream.cuda_stream)))
 
@@ -169,22 +179,12 @@ class LlmEngine:
         generation parameters.  ``last=True`` ends the prompt: needs ``row`` and takes
         ``prefill``'s generation parameters; the stream then continues as after one ``prefill`` of
         all the chunks' ids.  A call the device refuses changes nothing."""
-        if last:
-            if row is None:
-                raise ValueError("the final chunk needs a decode row")
-            if bool(grammar) != self._slot_grammar.get(slot, False) and 0 <= slot < self.max_slots:
-                self._check(self.lib.mx_llm_set_slot_grammar(self.h, slot, int(bool(grammar))))
-                self._slot_grammar[slot] = bool(grammar)
-        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
-        ck = _lib.PrefillChunk(slot=int(slot), row=int(row) if last else 0,
-                               ids_host=arr.ctypes.data, n_ids=len(arr), pos0=int(pos0),
-                               last=int(bool(last)))
-        if last:
-            ck.params = _lib.Sampling(temperature=float(temperature), top_p=float(top_p),
-                                      repetition_penalty=float(penalty),
-                                      seed=int(seed) & (2**64 - 1))
-            ck.ext = _lib.SamplingExt(top_k=int(top_k), min_p=float(min_p),
-                                      penalty_last_n=int(penalty_last_n))
+        if last and row is None:
+            raise ValueError("the final chunk needs a decode row")
+        ck = _lib.PrefillChunk()
+        keep = self._fill(ck, PrefillSegment(slot, row if last else 0, ids, penalty, temperature,
+                                             top_p, seed, top_k, min_p, penalty_last_n, grammar,
+                                             pos0), last=bool(last))
         self._check(self.lib.mx_llm_prefill_chunk(self.h, C.byref(ck),
                                                   C.c_void_p(stream.cuda_stream)))
 
@@ -600,7 +600,7 @@ class Synthesizer:
             nf = frames_for_slice(len(win) // 7, hi)  # the frames the kept slice depends on
             self.ring.codes[i][: 7 * nf] = win[: 7 * nf]
             self.snac.decode_ptr(self.ring.codes_dev[i], nf, 1, 0,
-                                 (nseed * 1000003 + widx[0]) & 0xFFFFFFFFFFFF,
+                                 window_seed(nseed, widx[0]),
                                  self.ring.pcm_dev[i], 0, lo, max(lo, hi), self.snac_stream)
             e = torch.cuda.Event()
             e.record(self.snac_stream)

@@ -13,6 +13,7 @@ tests/golden/speechpipe_golden.json, generated from the reference module):
 * ``window_valid``     = the range check of ``convert_to_audio`` (:108-111): codes in
   [0, 4096] (4096 passes the check although the codebook has 4096 rows).
 * ``frames_for_slice`` = how many of a window's frames the kept PCM slice depends on.
+* ``window_seed``      = the NoiseBlock noise seed of a stream's j-th window.
 """
 from __future__ import annotations
 
@@ -73,6 +74,11 @@ def frames_for_slice(n_frames: int, hi: int) -> int:
     """Frames of an ``n_frames`` window that samples [.., hi) depend on: the 49-code window
     speechpipe keeps [2048, 4096) of is decoded as its first 5 frames (2/7 less SNAC work)."""
     return min(n_frames, -(-hi // SAMPLES_PER_FRAME) + RIGHT_CONTEXT_FRAMES)
+
+
+def window_seed(noise_seed: int, j: int) -> int:
+    """Noise seed of a stream's j-th SNAC window (batching-invariant)."""
+    return (noise_seed * 1000003 + j) & 0xFFFFFFFFFFFF
 
 
 def deinterleave(win: List[int]):
