@@ -25,9 +25,6 @@ DEFS = (["-DMX_ROWS_TRACE=1"] if TRACE else []) + \
 SOURCES = ["capi.hip", "llm_kernels.hip", "rows_v4_dispatch.hip", "rows_v4_qkv.hip",
            "rows_v4_resid.hip", "rows_v4_silu.hip", "rows_v4_head.hip", "head_b1.hip",
            "sample_kernels.hip", "snac_kernels.hip", "snac_enc_kernels.hip", "engine_b1.hip"]
-HEADERS = ["mx_common.h", "mx_llm_kernels.h", "mx_snac_kernels.h", "mx_snac_enc_kernels.h",
-           "mx_rows_common.h",
-           "mx_rows_v4.inc", "mx_rows_v4_body.inc", "mx_engine.h"]
 ARCH = os.environ.get("MORPHEUS_MX_ARCH", "gfx950")
 
 
@@ -36,6 +33,12 @@ def _hipcc() -> str:
         if c and (os.path.sep not in c or os.path.exists(c)):
             return c
     raise RuntimeError("hipcc not found")
+
+
+def compile_flags() -> list:
+    """The flags every translation unit is compiled with (scripts/isa_parity.py reuses them)."""
+    return [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics",
+            "-Wno-unused-result"] + DEFS + ["-x", "hip"]
 
 
 def _obj(s: str) -> str:
@@ -83,9 +86,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for s in SOURCES:
         if not force and not _stale(s):
             continue
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17",
-               "-munsafe-fp-atomics", "-Wno-unused-result"] + DEFS + ["-x", "hip", "-c",
-               os.path.join(CSRC, s), "-o", _obj(s) + ".tmp"]
+        cmd = [_hipcc()] + compile_flags() + ["-c", os.path.join(CSRC, s), "-o", _obj(s) + ".tmp"]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((subprocess.Popen(cmd), cmd, s))

@@ -36,6 +36,7 @@
 // Every wait is bounded (100 MHz realtime clock): a stuck hand-off sets *status and every wave
 // leaves, so a launch always drains.
 #include "mx_common.h"
+#include "mx_epilogue.h"
 #include "mx_llm_kernels.h"
 #include "mx_engine.h"
 
@@ -54,26 +55,17 @@ enum { PH_QKV = 0, PH_ATT = 1, PH_H1 = 2, PH_ACT = 3, PH_H2 = 4 };
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_cvoid;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
 // ---- granules (8 bytes: value, tag), write-through stores / loads -------------------------
 __device__ __forceinline__ void gput(uint2* g, int i, float v, uint32_t tag) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(g, 0, 0x7fffffff, 0x00020000);
   __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(v), tag}, r, i * 8, 0, 16);
 }
-__device__ __forceinline__ u32x4v gget2(const uint2* g, int i) {  // granules i, i + 1
+__device__ __forceinline__ u32x4 gget2(const uint2* g, int i) {  // granules i, i + 1
   const __amdgpu_buffer_rsrc_t r =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2*>(g), 0, 0x7fffffff, 0x00020000);
   return __builtin_amdgcn_raw_buffer_load_b128(r, i * 8, 0, 16);
-}
-__device__ __forceinline__ void st_wt(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_wt(const float* p) {
-  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- LDS words shared by the waves of the workgroup ------------------------------------
@@ -212,13 +204,13 @@ __device__ __forceinline__ bool gather(const uint2* g, int n, uint32_t tag, floa
   if (skip) return true;  // timing experiment (EngineArgs::dbg & 1): no hand-off waits
   constexpr int B = 8;  // granule pairs in flight per thread (n <= 4096 in one round)
   for (int base = 2 * ct; base < n; base += 2 * 256 * B) {
-    u32x4v v[B];
+    u32x4 v[B];
     bool ok[B];
     float2 wv[B];
 #pragma unroll
     for (int j = 0; j < B; ++j) {
       const int i = base + 2 * 256 * j;
-      v[j] = i < n ? gget2(g, i) : u32x4v{0u, tag, 0u, tag};
+      v[j] = i < n ? gget2(g, i) : u32x4{0u, tag, 0u, tag};
       // the norm weights go out with the granules (not after the wait)
       wv[j] = (w && i < n) ? *reinterpret_cast<const float2*>(w + i) : make_float2(1.f, 1.f);
     }
@@ -262,14 +254,6 @@ __device__ __forceinline__ bool gather(const uint2* g, int n, uint32_t tag, floa
   }
   return true;
 }
-
-// Before a gather: poll one WITNESS granule per producer (the last of its contiguous range of
-// `per` outputs) instead of sweeping the whole vector, so 256 CUs waiting on an edge put ~4 KB
-// each per poll round on the fabric, not the vector (24-64 KB); then join the consumer barrier.
-// The sweep that follows is then almost always one pass.
-__device__ __forceinline__ bool witness(const uint2* g, int n, int per, uint32_t tag, int ct,
-                                        Ctl* ctl, int& gen, const Clock& clk, int* status,
-                                        bool skip);
 
 // 64-lane sum: the four in-row steps on DPP (quad_perm [1,0,3,2], [2,3,0,1], row_ror 4, 8:
 // VALU, no LDS round trip), the two cross-row steps as lane shuffles
@@ -327,14 +311,8 @@ __device__ __forceinline__ float4 slot_dot_t(const uint4* slot, const float4* X,
         if (F8) {
           const uint32_t wd[4] = {w[i][j].x, w[i][j].y, w[i][j].z, w[i][j].w};
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(wd[q], false);
-            const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(wd[q], true);
-            acc[j] = fmaf(lo.x, xq[i][q].x, acc[j]);
-            acc[j] = fmaf(lo.y, xq[i][q].y, acc[j]);
-            acc[j] = fmaf(hi.x, xq[i][q].z, acc[j]);
-            acc[j] = fmaf(hi.y, xq[i][q].w, acc[j]);
-          }
+          for (int q = 0; q < 4; ++q)
+            acc[j] = dot4_f8(wd[q], xq[i][q], acc[j]);
         } else {
           acc[j] = dot8(w[i][j], xq[i][0], xq[i][1], acc[j]);
         }
@@ -367,6 +345,10 @@ __device__ __forceinline__ float4 slot_dot(const uint4* slot, const float4* X, i
   return make_float4(0.f, 0.f, 0.f, 0.f);  // (no other shape passes the host-side check)
 }
 
+// Before a gather: poll one WITNESS granule per producer (the last of its contiguous range of
+// `per` outputs) instead of sweeping the whole vector, so 256 CUs waiting on an edge put ~4 KB
+// each per poll round on the fabric, not the vector (24-64 KB); then join the consumer barrier.
+// The sweep that follows is then almost always one pass.
 __device__ __forceinline__ bool witness(const uint2* g, int n, int per, uint32_t tag, int ct,
                                         Ctl* ctl, int& gen, const Clock& clk, int* status,
                                         bool skip) {
@@ -376,7 +358,7 @@ __device__ __forceinline__ bool witness(const uint2* g, int n, int per, uint32_t
     const int wi = min((i + 1) * per, n) - 1;
     int spins = 0;
     while (true) {
-      const u32x4v v = gget2(g, wi & ~1);
+      const u32x4 v = gget2(g, wi & ~1);
       if ((wi & 1 ? v.w : v.y) == tag) break;
       __builtin_amdgcn_s_sleep(2);
       if ((spins++ & 63) == 0 && (lds_ld(&ctl->abort_) || clk.expired())) {
@@ -387,21 +369,6 @@ __device__ __forceinline__ bool witness(const uint2* g, int n, int per, uint32_t
     }
   }
   return cbar(ctl, gen, clk, status);
-}
-
-__device__ __forceinline__ void split3(const float* x, bf16x8& f0, bf16x8& f1, bf16x8& f2) {
-  uint32_t w0[4], w1[4], w2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = x[2 * j], b = x[2 * j + 1];
-    w0[j] = pack2_bf16(a, b);
-    const float a1 = a - bf16_lo(w0[j]), b1 = b - bf16_hi(w0[j]);
-    w1[j] = pack2_bf16(a1, b1);
-    w2[j] = pack2_bf16(a1 - bf16_lo(w1[j]), b1 - bf16_hi(w1[j]));
-  }
-  f0 = __builtin_bit_cast(bf16x8, make_uint4(w0[0], w0[1], w0[2], w0[3]));
-  f1 = __builtin_bit_cast(bf16x8, make_uint4(w1[0], w1[1], w1[2], w1[3]));
-  f2 = __builtin_bit_cast(bf16x8, make_uint4(w2[0], w2[1], w2[2], w2[3]));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -594,7 +561,7 @@ __global__ __launch_bounds__(64 * (NC + NL), 1) void engine_kernel(EngineArgs a)
         if (lane == 0) ctl->ss[cw] = ss;
         if (!(ok = cbar(ctl, gen, clk, a.status))) break;
         if (st0) stamp(l, 1);
-        const float scale = 1.0f / sqrtf((ctl->ss[0] + ctl->ss[1] + ctl->ss[2] + ctl->ss[3]) / H + a.eps);
+        const float scale = rms_scale(ctl->ss[0] + ctl->ss[1] + ctl->ss[2] + ctl->ss[3], H, a.eps);
         const Ph& P = ph0;
         const int pos = L - 1;
         for (int s = 0; s < P.nslots; ++s, ++k) {
@@ -619,7 +586,7 @@ __global__ __launch_bounds__(64 * (NC + NL), 1) void engine_kernel(EngineArgs a)
               const int hh = n >> 7, within = n & 127, p = within >> 1;
               if (hh < a.heads + a.kv_heads) {
                 const float cs = ctl->rope[(n - P.r0) >> 1][0], sn = ctl->rope[(n - P.r0) >> 1][1];
-                const float o1 = x1 * cs - x2 * sn, o2 = x2 * cs + x1 * sn;
+                const float o1 = rope_lo(x1, x2, cs, sn), o2 = rope_hi(x1, x2, cs, sn);
                 if (hh < a.heads) {
                   gput(a.g_qkv, hh * 128 + p, o1, tg + PH_QKV);
                   gput(a.g_qkv, hh * 128 + p + 64, o2, tg + PH_QKV);
@@ -893,7 +860,7 @@ __global__ __launch_bounds__(64 * (NC + NL), 1) void engine_kernel(EngineArgs a)
         if (lane == 0) ctl->ss[cw] = ss;
         if (!(ok = cbar(ctl, gen, clk, a.status))) break;
         if (st0) stamp(l, 6);
-        const float scale = 1.0f / sqrtf((ctl->ss[0] + ctl->ss[1] + ctl->ss[2] + ctl->ss[3]) / H + a.eps);
+        const float scale = rms_scale(ctl->ss[0] + ctl->ss[1] + ctl->ss[2] + ctl->ss[3], H, a.eps);
         const Ph& P = ph2;
         for (int s = 0; s < P.nslots; ++s, ++k) {
           if (k % NC != cw) continue;
@@ -915,7 +882,7 @@ __global__ __launch_bounds__(64 * (NC + NL), 1) void engine_kernel(EngineArgs a)
               gt *= ctl->scl[l & 1][SC_GU + n - P.r0];
               up *= ctl->scl[l & 1][SC_GU + n + 1 - P.r0];
             }
-            gput(a.g_act, n >> 1, gt / (1.0f + expf(-gt)) * up, tg + PH_ACT);
+            gput(a.g_act, n >> 1, silu_mul(gt, up), tg + PH_ACT);
           }
         }
         if (!ok) break;

@@ -19,6 +19,7 @@
 // with 1.5-4 row groups per wave there is little stream to pipeline, and one block per CU
 // hides less latency than gemv1's many one-shot blocks.
 #include "mx_common.h"
+#include "mx_epilogue.h"
 #include "mx_llm_kernels.h"
 
 namespace mx {
@@ -122,12 +123,7 @@ __device__ __forceinline__ void process(const GemvArgs& a, const float4* xs, int
   }
   if (!on) return;
   const int id = a.id0 + g * RPW + ri;  // (the window's first row is id id0)
-  if (!grammar_allows(a.gram, sp, id)) return;  // outside the slot's allowed set: as -inf
-  float y = F8 ? v[0] * e.ws : v[0];
-  if (e.seen) y = y > 0.f ? y / pen : y * pen;
-  if (keep) a.logits[id] = y;
-  const unsigned long long key = argmax_key(y, (uint32_t)id);
-  best = key > best ? key : best;
+  head_candidate(a, sp, id, F8 ? v[0] * e.ws : v[0], e.seen, pen, keep, true, /*row*/ 0, 0, best);
 }
 
 template <int KCH, int RPW, bool F8>
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(NT, 1) void head_b1_kernel(GemvArgs a) {
   const bool on = lane % (64 / RPW) == 0;
   const int slot = a.row_slot[0];
   const float pen = a.penalty[slot];
-  const bool keep = a.logits && (a.logits_all || a.samp_temp[slot] > 0.f);
+  const bool keep = head_keep(a, slot);
   // the slot's allowed ids (wave-uniform, loaded with the slot's other constants: nothing of
   // the mask waits at the tail)
   const GrammarSpan sp = grammar_span(a.gram, grammar_origin(a.gram, slot), a.gram.origin ? a.row_pos[0] : 0);
@@ -171,22 +167,20 @@ __global__ __launch_bounds__(NT, 1) void head_b1_kernel(GemvArgs a) {
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < XPT; ++i)
-    if (tid + i * NT < XN)
-      ss += xv[i].x * xv[i].x + xv[i].y * xv[i].y + xv[i].z * xv[i].z + xv[i].w * xv[i].w;
+    if (tid + i * NT < XN) ss += sumsq4(xv[i]);
   ss = wave_sum(ss);
   if (lane == 0) red[wid] = ss;
   __syncthreads();
   float tot = 0.f;
 #pragma unroll
   for (int i = 0; i < WPB; ++i) tot += red[i];
-  const float scale = 1.0f / sqrtf(tot / (float)(KC * EPC) + a.eps);
+  const float scale = rms_scale(tot, KC * EPC, a.eps);
 #pragma unroll
   for (int i = 0; i < XPT; ++i) {
     const int idx = tid + i * NT;
     if (idx < XN) {
       float4 v = xv[i];
-      v.x = v.x * scale * nv[i].x; v.y = v.y * scale * nv[i].y;
-      v.z = v.z * scale * nv[i].z; v.w = v.w * scale * nv[i].w;
+      norm4(v, scale, nv[i]);
       xs[(idx % PL) * KC + idx / PL] = v;
     }
   }

@@ -10,6 +10,7 @@
 // not for MFMA: 16-byte non-temporal weight loads, activations staged once per block in
 // LDS (split lo/hi float4 planes -> conflict-free ds_read_b128), wave64 butterflies.
 #include "mx_common.h"
+#include "mx_epilogue.h"
 #include "mx_llm_kernels.h"
 
 #include <algorithm>
@@ -45,8 +46,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
         xlo[rt * K8 + c] = lo;
         xhi[rt * K8 + c] = hi;
         if (NORM) {
-          ss += lo.x * lo.x + lo.y * lo.y + lo.z * lo.z + lo.w * lo.w;
-          ss += hi.x * hi.x + hi.y * hi.y + hi.z * hi.z + hi.w * hi.w;
+          ss += sumsq4(lo);
+          ss += sumsq4(hi);
         }
       }
     } else {
@@ -60,17 +61,15 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
       if (lane == 0) red[wid] = ss;
       __syncthreads();
       const float tot = red[0] + red[1] + red[2] + red[3];
-      const float scale = 1.0f / sqrtf(tot / (float)a.K + a.eps);
+      const float scale = rms_scale(tot, a.K, a.eps);
       __syncthreads();
       if (rt < nr) {
         const float4* nw = reinterpret_cast<const float4*>(a.norm_w);
         for (int c = tid; c < K8; c += 256) {
           float4 lo = xlo[rt * K8 + c], hi = xhi[rt * K8 + c];
           const float4 wl = nw[2 * c], wh = nw[2 * c + 1];
-          lo.x = lo.x * scale * wl.x; lo.y = lo.y * scale * wl.y;
-          lo.z = lo.z * scale * wl.z; lo.w = lo.w * scale * wl.w;
-          hi.x = hi.x * scale * wh.x; hi.y = hi.y * scale * wh.y;
-          hi.z = hi.z * scale * wh.z; hi.w = hi.w * scale * wh.w;
+          norm4(lo, scale, wl);
+          norm4(hi, scale, wh);
           xlo[rt * K8 + c] = lo;
           xhi[rt * K8 + c] = hi;
         }
@@ -115,14 +114,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
             const uint32_t wd[4] = {w[i].x, w[i].y, w[i].z, w[i].w};
             const float4 xx[4] = {x0, x1, x2, x3};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(wd[q], false);
-              const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(wd[q], true);
-              acc[i][rt] = fmaf(lo.x, xx[q].x, acc[i][rt]);
-              acc[i][rt] = fmaf(lo.y, xx[q].y, acc[i][rt]);
-              acc[i][rt] = fmaf(hi.x, xx[q].z, acc[i][rt]);
-              acc[i][rt] = fmaf(hi.y, xx[q].w, acc[i][rt]);
-            }
+            for (int q = 0; q < 4; ++q)
+              acc[i][rt] = dot4_f8(wd[q], xx[q], acc[i][rt]);
           }
         }
       }
@@ -156,20 +149,15 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
           const int slot = a.row_slot[r0 + rt];
           const uint8_t* seen = a.seen + (size_t)slot * a.V;
           const float pen = a.penalty[slot];
-          const bool keep = a.logits && (a.logits_all || a.samp_temp[slot] > 0.f);
-          // ids outside a constrained slot's allowed set count as -inf: no key, no logit
+          const bool keep = head_keep(a, slot);
           const GrammarSpan sp = grammar_span(a.gram, grammar_origin(a.gram, slot),
                                               a.gram.origin ? a.row_pos[r0 + rt] : 0);
 #pragma unroll
           for (int i = 0; i < RPW; ++i) {
             const int n = n0 + i, id = a.id0 + n;  // (weight row n of the window is id id0 + n)
-            if (n < a.N && grammar_allows(a.gram, sp, id)) {
-              float v = acc[i][rt];
-              if (seen[id]) v = v > 0.f ? v / pen : v * pen;
-              if (keep && lane == 0) a.logits[(size_t)(r0 + rt) * a.V + id] = v;
-              const unsigned long long key = argmax_key(v, (uint32_t)id);
-              best[rt] = key > best[rt] ? key : best[rt];
-            }
+            if (n < a.N)
+              head_candidate(a, sp, id, acc[i][rt], seen[id], pen, keep, lane == 0,
+                             (size_t)(r0 + rt), a.V, best[rt]);
           }
         }
       }
@@ -187,39 +175,14 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
         } else if (EPI == EPI_SILU) {
 #pragma unroll
           for (int i = 0; i < RPW; i += 2) {
-            const float g = acc[i][rt], u = acc[i + 1][rt];
-            a.Y[(size_t)r * (a.N >> 1) + ((n0 + i) >> 1)] = g / (1.0f + expf(-g)) * u;
+            a.Y[(size_t)r * (a.N >> 1) + ((n0 + i) >> 1)] = silu_mul(acc[i][rt], acc[i + 1][rt]);
           }
         } else if (EPI == EPI_QKV) {
           const int slot = a.row_slot[r], pos = a.row_pos[r];
 #pragma unroll
-          for (int i = 0; i < RPW; i += 2) {
-            const int n = n0 + i;
-            const int hh = n >> 7, within = n & 127, p = within >> 1;
-            const float x1 = acc[i][rt], x2 = acc[i + 1][rt];
-            if (hh < a.heads + a.kv_heads) {
-              const float c = a.rope_cos[(size_t)pos * 64 + p];
-              const float s = a.rope_sin[(size_t)pos * 64 + p];
-              const float o1 = x1 * c - x2 * s;
-              const float o2 = x2 * c + x1 * s;
-              if (hh < a.heads) {
-                float* q = a.Q + ((size_t)r * a.heads + hh) * 128;
-                q[p] = o1;
-                q[p + 64] = o2;
-              } else {
-                uint16_t* k = a.kcache +
-                    ((size_t)slot * a.kv_heads + (hh - a.heads)) * a.max_pos * 128;
-                k[kv_k_off(pos, p)] = f32_to_bf16(o1);
-                k[kv_k_off(pos, p + 64)] = f32_to_bf16(o2);
-              }
-            } else {
-              // fragment-major chunks (mx_common.h kv_v_off, see attn_kernel)
-              uint16_t* v = a.vcache +
-                  ((size_t)slot * a.kv_heads + (hh - a.heads - a.kv_heads)) * 128 * a.max_pos;
-              v[kv_v_off(pos, within)] = f32_to_bf16(x1);
-              v[kv_v_off(pos, within + 1)] = f32_to_bf16(x2);
-            }
-          }
+          for (int i = 0; i < RPW; i += 2)
+            MX_QKV_PAIR(a, n0 + i, acc[i][rt], acc[i + 1][rt], slot, pos, r,
+                        a.rope_cos[(size_t)pos * 64 + p], a.rope_sin[(size_t)pos * 64 + p]);
         }
       }
     }
@@ -264,60 +227,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
 // addresses fixed by the kernel arguments (slot s, clamped to the host's bound att_nsm on the
 // row's splits and to the att_stride slots a kv head owns; slots past the bound re-read the
 // last one, which costs no second fetch), row_pos[0] is requested beside them, and
-// merge_apply drops the slots at or past the live count with selects on the loaded values --
-// a dead slot may hold anything (never written, a stale partial, NaN, Inf) and none of it
-// reaches M, den or num.
-template <int NSM>
-struct MergeIn {  // one 8-dim group's split partials, loaded
-  float2 ml[NSM];
-  float4 lo[NSM], hi[NSM];
-};
-template <int NSM>
-__device__ __forceinline__ void merge_load(const GemvArgs& a, int stride, int nb, int j, MergeIn<NSM>& in) {
-  const int GRP = a.heads / a.kv_heads;
-  const int hh = j >> 4, d0 = (j & 15) * 8;
-  const int kvh = hh / GRP, hin = hh - kvh * GRP;
-  // slot s of this kv head sits s * GRP (m, l) pairs / accumulator rows past slot 0: the lane's
-  // part of the address is formed once, the slot's part is wave-uniform
-  const size_t p0 = (size_t)kvh * stride * GRP + hin;
-  const float* ml0 = a.att_ml + p0 * 2;
-  const float* ac0 = a.att_acc + p0 * 128 + d0;
-#pragma unroll
-  for (int s = 0; s < NSM; ++s) {
-    const size_t so = (size_t)(min(s, nb - 1) * GRP);
-    in.ml[s] = *reinterpret_cast<const float2*>(ml0 + so * 2);
-    const float4* ac = reinterpret_cast<const float4*>(ac0 + so * 128);
-    in.lo[s] = ac[0];
-    in.hi[s] = ac[1];
-  }
-}
-template <int NSM, bool EARLY>
-__device__ __forceinline__ void merge_apply(const MergeIn<NSM>& in, int ns, float* x) {
-  float M = -INFINITY;
-#pragma unroll
-  for (int s = 0; s < NSM; ++s)
-    if (s < ns) M = fmaxf(M, in.ml[s].x);
-  float den = 0.f;
-  float num[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < NSM; ++s) {
-    // a dead slot enters as f = 0 times zeros (selects, not 0 * x: x may be NaN / Inf)
-    const bool live = !EARLY || s < ns;  // (!EARLY: a dead slot is a copy of the last live one)
-    const float f = s < ns ? expf(in.ml[s].x - M) : 0.f;
-    const float l = live ? in.ml[s].y : 0.f;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 lo = live ? in.lo[s] : z, hi = live ? in.hi[s] : z;
-    den = fmaf(f, l, den);
-    num[0] = fmaf(f, lo.x, num[0]); num[1] = fmaf(f, lo.y, num[1]);
-    num[2] = fmaf(f, lo.z, num[2]); num[3] = fmaf(f, lo.w, num[3]);
-    num[4] = fmaf(f, hi.x, num[4]); num[5] = fmaf(f, hi.y, num[5]);
-    num[6] = fmaf(f, hi.z, num[6]); num[7] = fmaf(f, hi.w, num[7]);
-  }
-  const float inv = 1.0f / den;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = num[i] * inv;
-}
-
+// merge_apply (mx_epilogue.h) drops the slots at or past the live count with selects on the
+// loaded values -- a dead slot may hold anything (never written, a stale partial, NaN, Inf) and
+// none of it reaches M, den or num.
 template <int KCH, int RPW, int EPI, bool NORM, int WPB, bool F8, int NSM = 0>
 __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
   constexpr int NT = WPB * 64;
@@ -411,9 +323,7 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
     for (int i = 0; i < XPT; ++i) {
       if (tid + i * NT < KC) {
 #pragma unroll
-        for (int q = 0; q < PL; ++q)
-          ss += xv[i][q].x * xv[i][q].x + xv[i][q].y * xv[i][q].y + xv[i][q].z * xv[i][q].z +
-                xv[i][q].w * xv[i][q].w;
+        for (int q = 0; q < PL; ++q) ss += sumsq4(xv[i][q]);
       }
     }
     ss = wave_sum(ss);
@@ -422,7 +332,7 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
     float tot = 0.f;
 #pragma unroll
     for (int i = 0; i < WPB; ++i) tot += red[i];
-    scale = 1.0f / sqrtf(tot / (float)(KC * EPC) + a.eps);
+    scale = rms_scale(tot, KC * EPC, a.eps);
   }
 #pragma unroll
   for (int i = 0; i < XPT && NSM == 0; ++i) {
@@ -431,10 +341,7 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
 #pragma unroll
       for (int q = 0; q < PL; ++q) {
         float4 v = xv[i][q];
-        if (NORM) {
-          v.x = v.x * scale * nv[i][q].x; v.y = v.y * scale * nv[i][q].y;
-          v.z = v.z * scale * nv[i][q].z; v.w = v.w * scale * nv[i][q].w;
-        }
+        if (NORM) norm4(v, scale, nv[i][q]);
         xs[q * KC + m] = v;
       }
     }
@@ -453,6 +360,8 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       if (F8) {
+        // (dot4_f8's statements, kept here: through the function eight instantiations of this
+        // kernel come out with the row-scale multiply's operands swapped)
         const uint32_t wd[4] = {w[r][c].x, w[r][c].y, w[r][c].z, w[r][c].w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -484,38 +393,13 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
     for (int r = 0; r < RPW; ++r) a.Y[n0 + r] = res[r] + acc[r];
   } else if (EPI == EPI_SILU) {
 #pragma unroll
-    for (int r = 0; r < RPW; r += 2) {
-      const float gt = acc[r], up = acc[r + 1];
-      a.Y[(n0 + r) >> 1] = gt / (1.0f + expf(-gt)) * up;
-    }
+    for (int r = 0; r < RPW; r += 2) a.Y[(n0 + r) >> 1] = silu_mul(acc[r], acc[r + 1]);
   } else if (EPI == EPI_QKV) {
     const int slot = a.row_slot[0], pos = a.row_pos[0];
 #pragma unroll
-    for (int r = 0; r < RPW; r += 2) {
-      const int n = n0 + r;
-      const int hh = n >> 7, within = n & 127, p = within >> 1;
-      const float x1 = acc[r], x2 = acc[r + 1];
-      if (hh < a.heads + a.kv_heads) {
-        const float cs = a.rope_cos[(size_t)pos * 64 + p];
-        const float sn = a.rope_sin[(size_t)pos * 64 + p];
-        const float o1 = x1 * cs - x2 * sn;
-        const float o2 = x2 * cs + x1 * sn;
-        if (hh < a.heads) {
-          float* q = a.Q + (size_t)hh * 128;
-          q[p] = o1;
-          q[p + 64] = o2;
-        } else {
-          uint16_t* k = a.kcache + ((size_t)slot * a.kv_heads + (hh - a.heads)) * a.max_pos * 128;
-          k[kv_k_off(pos, p)] = f32_to_bf16(o1);
-          k[kv_k_off(pos, p + 64)] = f32_to_bf16(o2);
-        }
-      } else {
-        uint16_t* v = a.vcache +
-            ((size_t)slot * a.kv_heads + (hh - a.heads - a.kv_heads)) * 128 * a.max_pos;
-        v[kv_v_off(pos, within)] = f32_to_bf16(x1);
-        v[kv_v_off(pos, within + 1)] = f32_to_bf16(x2);
-      }
-    }
+    for (int r = 0; r < RPW; r += 2)
+      MX_QKV_PAIR(a, n0 + r, acc[r], acc[r + 1], slot, pos, 0,
+                  a.rope_cos[(size_t)pos * 64 + p], a.rope_sin[(size_t)pos * 64 + p]);
   }
 }
 
@@ -537,31 +421,6 @@ __global__ __launch_bounds__(WPB * 64) void gemv1_kernel(GemvArgs a) {
 //   arriver merges every split with sc1 loads (MI355X_MICROARCH.md "Valid forms", row 1),
 //   then resets the counter for the next launch.
 // ---------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void st_wt(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_wt(const float* p) {
-  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// x = p0 + p1 + p2 with p_i bf16 (exact to fp32 rounding); 8 values -> three fragments
-__device__ __forceinline__ void split3(const float* x, bf16x8& f0, bf16x8& f1, bf16x8& f2) {
-  uint32_t w0[4], w1[4], w2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = x[2 * j], b = x[2 * j + 1];
-    w0[j] = pack2_bf16(a, b);
-    const float a1 = a - bf16_lo(w0[j]), b1 = b - bf16_hi(w0[j]);
-    w1[j] = pack2_bf16(a1, b1);
-    w2[j] = pack2_bf16(a1 - bf16_lo(w1[j]), b1 - bf16_hi(w1[j]));
-  }
-  f0 = __builtin_bit_cast(bf16x8, make_uint4(w0[0], w0[1], w0[2], w0[3]));
-  f1 = __builtin_bit_cast(bf16x8, make_uint4(w1[0], w1[1], w1[2], w1[3]));
-  f2 = __builtin_bit_cast(bf16x8, make_uint4(w2[0], w2[1], w2[2], w2[3]));
-}
-
 // One block = NW waves over S = 32 NW CPW positions of one (row, kv head); wave w takes the
 // 32-position chunks w, w + NW, ... (CPW of them), with the next chunk's K / V^T loads in
 // flight under the current chunk's MFMAs and softmax.  NW = 8, CPW = 4 covers
@@ -578,7 +437,6 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
   // the loads need in one batch (the empty asm holds them in scalar registers from here on;
   // global-typed, so the loads behind it stay global_load), then the row's position and slot
   // together.  The Q loads (not the qkv_parts path) depend on neither and go out in between.
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(1))) const u32x4 gu4;
   typedef __attribute__((address_space(1))) const f32x4 gf4;
   int L = a.row_pos[r] + 1;
@@ -654,7 +512,7 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
 #pragma unroll
     for (int kc = 0; kc < ATT_QKV_NKC_MAX; ++kc)
       if (kc < nk) ss += ssv[kc];
-    const float scl = 1.0f / sqrtf(ss / (float)a.hidden + a.eps);
+    const float scl = rms_scale(ss, a.hidden, a.eps);
     auto pair = [&](int idx, float& x1, float& x2) {
       float2 v[ATT_QKV_NKC_MAX];
 #pragma unroll
@@ -678,8 +536,8 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
       float x1, x2;
       pair((kvh * GRP + h) * 128 + 2 * p, x1, x2);
       const float cs = a.rope_cos[(size_t)pos * 64 + p], sn = a.rope_sin[(size_t)pos * 64 + p];
-      qs[h][p] = x1 * cs - x2 * sn;
-      qs[h][p + 64] = x2 * cs + x1 * sn;
+      qs[h][p] = rope_lo(x1, x2, cs, sn);
+      qs[h][p + 64] = rope_hi(x1, x2, cs, sn);
     }
     if (split == pos / S && wid == ((((pos & ~31) - split * S) >> 5) % NW)) {
       const int p = lane;  // k dims (p, p + 64); v dims (2p, 2p + 1)
@@ -689,10 +547,10 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnArgs a) {
       const float cs = a.rope_cos[(size_t)pos * 64 + p], sn = a.rope_sin[(size_t)pos * 64 + p];
       uint16_t* kcw = const_cast<uint16_t*>(a.kcache) + head * a.max_pos * 128;
       uint16_t* vcw = const_cast<uint16_t*>(a.vcache) + head * a.max_pos * 128;
-      kcw[kv_k_off(pos, p)] = f32_to_bf16(k1 * cs - k2 * sn);
-      kcw[kv_k_off(pos, p + 64)] = f32_to_bf16(k2 * cs + k1 * sn);
-      vcw[kv_v_off(pos, 2 * p)] = f32_to_bf16(v1);
-      vcw[kv_v_off(pos, 2 * p + 1)] = f32_to_bf16(v2);
+      kv_put_k(kcw, pos, p, rope_lo(k1, k2, cs, sn));
+      kv_put_k(kcw, pos, p + 64, rope_hi(k1, k2, cs, sn));
+      kv_put_v(vcw, pos, 2 * p, v1);
+      kv_put_v(vcw, pos, 2 * p + 1, v2);
       if (late0) load_kv(base0, 0);
     }
     __syncthreads();

@@ -20,6 +20,10 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 }
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+// MFMA operand / result fragments and 16 raw bytes, the one spelling of each
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // two fp32 -> packed bf16x2 (lo in bits 0-15), one v_cvt_pk_bf16_f32
 __device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) {
   const bf16x2_t v = __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t);
@@ -57,6 +61,37 @@ __device__ __forceinline__ float dot8(const uint4 w, const float4 a, const float
   return acc;
 }
 
+// dot of 4 e4m3 weights (one dword of a 16-byte load of 16) with 4 fp32 activations; the
+// conversion (v_cvt_pk_f32_fp8) is exact.  One dword and one plane per call, the plane by
+// reference: with the 16-byte load and the four planes passed by value the one-row kernels and
+// the engine come out with their LDS reads and conversions in another order (the float4s are
+// then split at the use, not at the load).  head_b1.hip keeps its own packed-FMA sequence on
+// purpose.
+__device__ __forceinline__ float dot4_f8(uint32_t w, const float4& x, float acc) {
+  const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
+  const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+  acc = fmaf(lo.x, x.x, acc);
+  acc = fmaf(lo.y, x.y, acc);
+  acc = fmaf(hi.x, x.z, acc);
+  acc = fmaf(hi.y, x.w, acc);
+  return acc;
+}
+
+// RMSNorm pieces: a float4's sum of squares, the factor from a row's sum of squares over K
+// elements, and v * scale * w
+__device__ __forceinline__ float sumsq4(const float4& v) {
+  return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+}
+__device__ __forceinline__ float rms_scale(float ss, int K, float eps) {
+  return 1.0f / sqrtf(ss / (float)K + eps);
+}
+__device__ __forceinline__ void norm4(float4& v, float scale, const float4& w) {
+  v.x = v.x * scale * w.x; v.y = v.y * scale * w.y;
+  v.z = v.z * scale * w.z; v.w = v.w * scale * w.w;
+}
+// SiLU(g) * u of a gate / up pair
+__device__ __forceinline__ float silu_mul(float g, float u) { return g / (1.0f + expf(-g)) * u; }
+
 // Order-preserving float key for a 64-bit atomicMax argmax: high word = value,
 // low word = ~index so that equal values resolve to the SMALLEST index (torch.argmax).
 __device__ __forceinline__ unsigned long long argmax_key(float v, uint32_t idx) {
@@ -69,10 +104,37 @@ __device__ __forceinline__ uint32_t argmax_index(unsigned long long key) {
 }
 
 // Streaming (read-once) 16-byte load of weights: non-temporal hint.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 load_nt(const uint4* p) {
   const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
   return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// write-through (sc1) scalar-sized store / load of a value another block reads in this launch
+// (MI355X_MICROARCH.md "Valid forms" row 1)
+__device__ __forceinline__ void st_wt(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float ld_wt(const float* p) {
+  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// x = p0 + p1 + p2 with p_i bf16 (exact to fp32 rounding); 8 values -> three fragments.
+// (mx_rows_common.h's split_parts<3> is the same arithmetic written as a loop over the parts;
+// the two stay apart: through split_parts the attention kernels get a different register
+// allocation, NumVgprs 253 -> 244 and 255 -> 247.)
+__device__ __forceinline__ void split3(const float* x, bf16x8& f0, bf16x8& f1, bf16x8& f2) {
+  uint32_t w0[4], w1[4], w2[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float a = x[2 * j], b = x[2 * j + 1];
+    w0[j] = pack2_bf16(a, b);
+    const float a1 = a - bf16_lo(w0[j]), b1 = b - bf16_hi(w0[j]);
+    w1[j] = pack2_bf16(a1, b1);
+    w2[j] = pack2_bf16(a1 - bf16_lo(w1[j]), b1 - bf16_hi(w1[j]));
+  }
+  f0 = __builtin_bit_cast(bf16x8, make_uint4(w0[0], w0[1], w0[2], w0[3]));
+  f1 = __builtin_bit_cast(bf16x8, make_uint4(w1[0], w1[1], w1[2], w1[3]));
+  f2 = __builtin_bit_cast(bf16x8, make_uint4(w2[0], w2[1], w2[2], w2[3]));
 }
 
 // KV cache layout.  One (slot, kv head) holds max_pos x 128 bf16 of K and the

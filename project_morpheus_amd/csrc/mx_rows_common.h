@@ -2,15 +2,15 @@
 // epilogues (RoPE + KV append, residual, SiLU*up, penalty + argmax), write-through partials.
 #pragma once
 #include "mx_common.h"
+#include "mx_epilogue.h"
 #include "mx_llm_kernels.h"
 
 namespace mx {
 namespace rows {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // x[0..7] -> NPART bf16x8 fragments with x = sum of parts (to fp32 rounding for NPART 3)
+// (mx_common.h's split3 is the three-part case unrolled by hand; they stay two functions, see
+// there)
 template <int NPART>
 __device__ __forceinline__ void split_parts(float* x, bf16x8* f) {
 #pragma unroll
@@ -71,7 +71,7 @@ __device__ __forceinline__ void argmax_operands(const GemvArgs& a, EpiPre<MT, NT
   for (int nt = 0; nt < NT; ++nt) {
     const int slot = P.aslot[nt % ANT];
     P.apen[nt % ANT] = a.penalty[slot];
-    P.akeep[nt % ANT] = a.logits && (a.logits_all || a.samp_temp[slot] > 0.f);
+    P.akeep[nt % ANT] = head_keep(a, slot);
     if constexpr (GRAM) P.alo[nt % ANT] = grammar_span(a.gram, a.gram.origin[slot], P.alo[nt % ANT]).lo;
     // (weight row n of a row window is id id0 + n; id0 is a multiple of 4.  Only the grammar
     // kernels run a window: the others have id0 = 0 and V = N)
@@ -170,40 +170,16 @@ __device__ __forceinline__ void rows_epilogue(const GemvArgs& a, f32x4 (&acc)[MT
               P.y[mt % (EPI == EPI_RESID ? MT : 1)][nt % (EPI == EPI_RESID ? NT : 1)][i] + v[i];
       } else if (EPI == EPI_SILU) {
 #pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-          const float gt = v[i], up = v[i + 1];
-          a.Y[(size_t)b * (a.N >> 1) + ((nb + i) >> 1)] = gt / (1.0f + expf(-gt)) * up;
-        }
+        for (int i = 0; i < 4; i += 2)
+          a.Y[(size_t)b * (a.N >> 1) + ((nb + i) >> 1)] = silu_mul(v[i], v[i + 1]);
       } else if (EPI == EPI_QKV) {
         const int slot = P.slot[nt % (EPI == EPI_QKV ? NT : 1)];
         const int pos = P.pos[nt % (EPI == EPI_QKV ? NT : 1)];
 #pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-          const int n = nb + i;
-          const int hh = n >> 7, within = n & 127, p = within >> 1;
-          const float x1 = v[i], x2 = v[i + 1];
-          if (hh < a.heads + a.kv_heads) {
-            const float cs = P.cs[mt % (EPI == EPI_QKV ? MT : 1)][nt % (EPI == EPI_QKV ? NT : 1)][i >> 1];
-            const float sn = P.sn[mt % (EPI == EPI_QKV ? MT : 1)][nt % (EPI == EPI_QKV ? NT : 1)][i >> 1];
-            const float o1 = x1 * cs - x2 * sn;
-            const float o2 = x2 * cs + x1 * sn;
-            if (hh < a.heads) {
-              float* q = a.Q + ((size_t)b * a.heads + hh) * 128;
-              q[p] = o1;
-              q[p + 64] = o2;
-            } else {
-              uint16_t* kc = a.kcache +
-                  ((size_t)slot * a.kv_heads + (hh - a.heads)) * a.max_pos * 128;
-              kc[kv_k_off(pos, p)] = f32_to_bf16(o1);
-              kc[kv_k_off(pos, p + 64)] = f32_to_bf16(o2);
-            }
-          } else {
-            uint16_t* vc = a.vcache +
-                ((size_t)slot * a.kv_heads + (hh - a.heads - a.kv_heads)) * 128 * a.max_pos;
-            vc[kv_v_off(pos, within)] = f32_to_bf16(x1);
-            vc[kv_v_off(pos, within + 1)] = f32_to_bf16(x2);
-          }
-        }
+        for (int i = 0; i < 4; i += 2)
+          MX_QKV_PAIR(a, nb + i, v[i], v[i + 1], slot, pos, b,
+                      P.cs[mt % (EPI == EPI_QKV ? MT : 1)][nt % (EPI == EPI_QKV ? NT : 1)][i >> 1],
+                      P.sn[mt % (EPI == EPI_QKV ? MT : 1)][nt % (EPI == EPI_QKV ? NT : 1)][i >> 1]);
       } else if (EPI == EPI_ARGMAX) {
         constexpr int ANT = EPI == EPI_ARGMAX ? NT : 1, AMT = EPI == EPI_ARGMAX ? MT : 1;
         const float pen = P.apen[nt % ANT];
@@ -214,13 +190,9 @@ __device__ __forceinline__ void rows_epilogue(const GemvArgs& a, f32x4 (&acc)[MT
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int n = nb + i, id = id0 + n;
-          // (ids outside a constrained slot's allowed set count as -inf: no key, no logit)
-          if (n >= a.N || (GRAM && !grammar_allows(a.gram, sp, id))) continue;
-          float x = v[i];
-          if ((sn >> (8 * i)) & 0xffu) x = x > 0.f ? x / pen : x * pen;
-          if (keep) a.logits[(size_t)b * V + id] = x;
-          const unsigned long long key = argmax_key(x, (uint32_t)id);
-          best[nt] = key > best[nt] ? key : best[nt];
+          if (n >= a.N) continue;
+          head_candidate(a, sp, id, v[i], (sn >> (8 * i)) & 0xffu, pen, keep, true, (size_t)b,
+                         V, best[nt]);
         }
       }
     }
@@ -252,7 +224,6 @@ __device__ __forceinline__ void rows_epilogue(const GemvArgs& a, f32x4 (&acc)[MT
   }
 }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // 16-byte write-through (sc1) store / load of a partial-tile quad (MI355X_MICROARCH.md
 // "Valid forms" row 1 with 16-B accesses)
 __device__ __forceinline__ void st4_wt(float* base, size_t idx, const f32x4& v) {
@@ -263,12 +234,6 @@ __device__ __forceinline__ f32x4 ld4_wt(const float* base, size_t idx) {
   const __amdgpu_buffer_rsrc_t r =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(idx * 4), 0, 16));
-}
-__device__ __forceinline__ void st_wt(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_wt(const float* p) {
-  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace rows

@@ -69,50 +69,7 @@ using namespace rows;
 // before the main loop the block merges its K range for its 16 rows into LDS -- the partial
 // loads go out first, the first weight sub-chunks behind them -- and the activation pieces are
 // then read from there.  The attention takes no ticket and runs no last-arriver merge.
-template <int NSM>
-struct RowMergeIn {  // one (row, 8-dim group)'s split partials
-  float2 ml[NSM];
-  float4 lo[NSM], hi[NSM];
-};
-template <int NSM>
-__device__ __forceinline__ int row_merge_load(const GemvArgs& a, int b, int k, RowMergeIn<NSM>& in) {
-  const int GRP = a.heads / a.kv_heads;
-  const int hh = k >> 7, d0 = k & 127;
-  const int kvh = hh / GRP, hin = hh - kvh * GRP;
-  const int ns = (a.row_pos[b] + a.att_S) / a.att_S;  // splits of this row's L = pos + 1
-  const size_t pb = ((size_t)b * a.kv_heads + kvh) * a.att_stride;
-#pragma unroll
-  for (int s = 0; s < NSM; ++s) {
-    const size_t sp = pb + min(s, ns - 1);
-    in.ml[s] = *reinterpret_cast<const float2*>(a.att_ml + (sp * GRP + hin) * 2);
-    const float4* ac = reinterpret_cast<const float4*>(a.att_acc + (sp * GRP + hin) * 128 + d0);
-    in.lo[s] = ac[0];
-    in.hi[s] = ac[1];
-  }
-  return ns;
-}
-template <int NSM>
-__device__ __forceinline__ void row_merge_apply(const RowMergeIn<NSM>& in, int ns, float4& lo, float4& hi) {
-  float M = -INFINITY;
-#pragma unroll
-  for (int s = 0; s < NSM; ++s)
-    if (s < ns) M = fmaxf(M, in.ml[s].x);
-  float den = 0.f;
-  float4 nl = make_float4(0.f, 0.f, 0.f, 0.f), nh = nl;
-#pragma unroll
-  for (int s = 0; s < NSM; ++s) {
-    const float f = s < ns ? expf(in.ml[s].x - M) : 0.f;
-    den = fmaf(f, in.ml[s].y, den);
-    nl.x = fmaf(f, in.lo[s].x, nl.x); nl.y = fmaf(f, in.lo[s].y, nl.y);
-    nl.z = fmaf(f, in.lo[s].z, nl.z); nl.w = fmaf(f, in.lo[s].w, nl.w);
-    nh.x = fmaf(f, in.hi[s].x, nh.x); nh.y = fmaf(f, in.hi[s].y, nh.y);
-    nh.z = fmaf(f, in.hi[s].z, nh.z); nh.w = fmaf(f, in.hi[s].w, nh.w);
-  }
-  const float inv = 1.0f / den;
-  lo = make_float4(nl.x * inv, nl.y * inv, nl.z * inv, nl.w * inv);
-  hi = make_float4(nh.x * inv, nh.y * inv, nh.z * inv, nh.w * inv);
-}
-
+// (MergeIn, row_merge_load and row_merge_apply: mx_epilogue.h.)
 // The body is mx_rows_v4_body.inc.  GRAM (gemm_rows_gram_kernel): the lm_head of a context that
 // carries a code grammar -- a row window of the weights and the per-row mask; every other launch
 // runs gemm_rows_kernel, which has neither.

@@ -181,7 +181,7 @@
     // the block's K range for its 16 rows: 16 x SUB x 16 groups of 8 dims, the partial loads
     // first, the first weight sub-chunks behind them, then the merge into LDS
     constexpr int MI = (16 * SUB * 16 + 511) / 512;
-    RowMergeIn<NSM> mi[MI];
+    MergeIn<NSM> mi[MI];
     int mns[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -420,7 +420,7 @@
   float scale[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
-    scale[nt] = NORM ? 1.0f / sqrtf(ss[nt] / (float)a.K + a.eps) : 1.f;
+    scale[nt] = NORM ? rms_scale(ss[nt], a.K, a.eps) : 1.f;
   rows_epilogue<MT, NT, EPI, GRAM>(a, acc, scale, n0, r0, c, g, pre);
 #if MX_ROWS_TRACE
   if (a.trace) {

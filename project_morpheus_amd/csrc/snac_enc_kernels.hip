@@ -14,8 +14,6 @@
 
 namespace mx {
 
-using rows::bf16x8;
-using rows::f32x4;
 
 // ---------------------------------------------------------------------------------
 // Stem: conv k7 pad 3, 1 -> 48.  Block = 64 samples x 48 channels (12 channel quads x 16 row

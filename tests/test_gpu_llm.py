@@ -276,7 +276,7 @@ def test_rows_merge_straddling_splits_orpheus_width(case):
     """The generation-4 merging o-projection (rows_merge, the default) where the rows of one
     launch have different split counts: gemm_rows_kernel<1,1,1,false,3,false,2,NSM> with
     NSM 2 (rows of 1 and 2 splits) and NSM 4 (rows of 1, 2, 3 and 4 splits): the clamped
-    partial loads and the s < ns skip of mx_rows_v4.inc row_merge_load / row_merge_apply."""
+    partial loads and the s < ns skip of mx_epilogue.h row_merge_load / row_merge_apply."""
     from _dispatch import ORPHEUS_16K, att_shape, DEFAULTS
     lens, steps = STRADDLE[case]
     o = dict(DEFAULTS, att_nw6=0)  # the 256-position splits of 8-wave blocks
